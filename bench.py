@@ -20,6 +20,13 @@ At N > 1 that job runs through both fixed-job routes of heracles_amd.distributed
 -- `value` is the better of the two, named in config.parallelism; both are in "routes".  The job that GROWS with N (every rank
 brings its own 20 maps, pairs grow as N^2) is reported beside it as `value_weak` with its pair count and a per-GPU transform rate;
 `--scaling weak` makes that figure `value` instead.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the per-family kernel times of the
+timed steps).  Everything else -- verification against direct sums and the CPU oracle, the CPU baselines, the host -> host, niter = 3
+and single-map legs, the mixing-matrix builds, the roofline and measured peaks, and at N > 1 the growing job when it is not `value`
+and the cross-check of the two routes -- runs only with `--full` (the `--no-*` switches then drop single legs of it).
+`--dump-outputs DIR` writes what the timed path returned in its last step (the Cl rows; at N = 1 also a fixed, seeded sample of the
+alms) as DIR/<name>.npy in float64, at most 64 MB in all; the inputs are seeded, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -65,7 +72,41 @@ def parse():
     p.add_argument("--no-niter3", action="store_true", help="skip the niter = 3 leg (the 20-map job with healpy's default iterations)")
     p.add_argument("--launch-check", action="store_true", help="every rank checks its rendezvous variables and exits (rank 0 prints them); no GPU is touched")
     p.add_argument("--generic-weights", action="store_true", help="pixel weights without the symmetry of healpy's files (generic path of the ring kernels)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beyond the headline figure: verification, CPU baselines, host -> host, niter = 3, single-map "
+                        "transforms, mixing matrices, roofline, measured peaks and, at N > 1, the growing job and the cross-check of the routes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float64, <= 64 MB)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if not args.full:
+        # a plain run measures the headline figure only: every optional leg is off
+        args.no_cpu_baseline = args.no_mixmat = args.no_host_leg = args.no_verify = args.no_single = args.no_niter3 = True
+    return args
+
+
+DUMP_CL_MAX = 1 << 22      # float64 elements of the Cl rows written in full (32 MiB); a larger result is sampled
+DUMP_ALM_SAMPLE = 1 << 19  # complex alms sampled per spin (8 MiB each as (n, 2) float64)
+
+
+def sample_index(n, k, seed):
+    """a fixed, seeded, sorted choice of min(n, k) of n flat indices (all of them when n <= k)"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def cl_for_dump(cl):
+    """the Cl rows in full, or a fixed, seeded sample of their elements when they exceed DUMP_CL_MAX"""
+    return cl if cl.size <= DUMP_CL_MAX else cl.reshape(-1)[sample_index(cl.size, DUMP_CL_MAX, 1)]
+
+
+def dump_outputs(path, arrays):
+    """write each array as float64 to path/<name>.npy"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_engines():
@@ -337,17 +378,20 @@ def main():
         nbins = 13
     spins = per_set * nsets
     steps1 = args.steps if (world == 1 or args.scaling == "weak") else (args.weak_steps or min(args.steps, 5))
+    # the first leg is the headline at N = 1 and with --scaling weak; at N > 1 with strong scaling it is a side figure (--full only)
+    first_leg = world == 1 or args.scaling == "weak" or args.full
     nmaps_total = len(spins)
     work = hxd.ShardedTwoPoint(spins, world, rank, nlm, lmax)
     mine = work.local_maps
     n0 = sum(1 for g in mine if spins[g] == 0)
     n2 = len(mine) - n0
-    # synthetic inputs, resident in HBM (seeded by rank; which seed a map has does not matter to the metric)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(50 + rank)
-    maps0 = torch.randn((n0, npix), dtype=torch.float64, device=dev, generator=gen)
-    maps2 = torch.randn((n2, 2, npix), dtype=torch.float64, device=dev, generator=gen)
-    alm0, alm2 = work.local_alm_views(dev)
+    if first_leg:
+        # synthetic inputs, resident in HBM (seeded by rank; which seed a map has does not matter to the metric)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(50 + rank)
+        maps0 = torch.randn((n0, npix), dtype=torch.float64, device=dev, generator=gen)
+        maps2 = torch.randn((n2, 2, npix), dtype=torch.float64, device=dev, generator=gen)
+        alm0, alm2 = work.local_alm_views(dev)
     # Pixel weights in the timed path: the reference always transforms with use_pixel_weights=True (heracles/healpy.py:186).
     # healpy's weight files are not available offline; a synthetic file of the same FORMAT stands in: random values (1e-3) in
     # healpy's compressed layout, expanded by the library exactly as a real file would be (heracles_amd.weights) -- so the full-sky
@@ -418,46 +462,59 @@ def main():
         return e_, n_
 
     weak_error = None
-    try:
-        if os.environ.get("HX_BENCH_FAIL_WEAK") == "1" and world > 1:  # (test hook: the growing job fails on every rank alike)
-            raise RuntimeError("HX_BENCH_FAIL_WEAK")
-        for _ in range(args.warmup):
-            step()
-        hx._lib.profile_enable(True)
-        hx._lib.profile_reset()
-        dt, cls = timed(step, steps1, 0)
-        cls = None if cls is None else np.array(cls)  # (a copy for the checks below: the page-locked array belongs to the steps)
-        hx._lib.profile_enable(False)
-    except Exception as exc:  # noqa: BLE001
-        # N > 1 only: the job that grows with N is the side figure (`value_weak`); if it fails -- on every rank alike: its collectives have
-        # not run over RCCL before the driver's first N > 1 run -- the fixed job below still gets its line.  The per-GPU kernel figures
-        # then come from the local transforms alone.
-        if world == 1:
-            raise
-        weak_error = f"{type(exc).__name__}: {exc}"[:400]
-    # a failure on ONE rank must not go on into the collectives of the routes below while the others are elsewhere: unanimous or out
-    if agree_or_leave(weak_error is None, "weak-leg"):
-        weak_error = weak_error or "failed on every rank"
-        hx._lib.profile_enable(True)
-        hx._lib.profile_reset()
-        for _ in range(steps1):
-            if n2:
-                plan.map2alm(maps2.view(2 * n2, npix), 2, pix_weights=pw, out=alm2.view(2 * n2, nlm))
-            if n0:
-                plan.map2alm(maps0, 0, pix_weights=pw, out=alm0)
-        torch.cuda.synchronize()
-        hx._lib.profile_enable(False)
-        dt, cls = float("nan"), None
+    dt, cls = float("nan"), None
+    if first_leg:
+        try:
+            if os.environ.get("HX_BENCH_FAIL_WEAK") == "1" and world > 1:  # (test hook: the growing job fails on every rank alike)
+                raise RuntimeError("HX_BENCH_FAIL_WEAK")
+            for _ in range(args.warmup):
+                step()
+            hx._lib.profile_enable(True)
+            hx._lib.profile_reset()
+            dt, cls = timed(step, steps1, 0)
+            cls = None if cls is None else np.array(cls)  # (a copy for the checks below: the page-locked array belongs to the steps)
+            hx._lib.profile_enable(False)
+        except Exception as exc:  # noqa: BLE001
+            # N > 1 only: the job that grows with N is the side figure (`value_weak`); if it fails -- on every rank alike: its collectives have
+            # not run over RCCL before the driver's first N > 1 run -- the fixed job below still gets its line.  The per-GPU kernel figures
+            # then come from the local transforms alone.
+            if world == 1:
+                raise
+            weak_error = f"{type(exc).__name__}: {exc}"[:400]
+        # a failure on ONE rank must not go on into the collectives of the routes below while the others are elsewhere: unanimous or out
+        if agree_or_leave(weak_error is None, "weak-leg"):
+            weak_error = weak_error or "failed on every rank"
+            hx._lib.profile_enable(True)
+            hx._lib.profile_reset()
+            for _ in range(steps1):
+                if n2:
+                    plan.map2alm(maps2.view(2 * n2, npix), 2, pix_weights=pw, out=alm2.view(2 * n2, nlm))
+                if n0:
+                    plan.map2alm(maps0, 0, pix_weights=pw, out=alm0)
+            torch.cuda.synchronize()
+            hx._lib.profile_enable(False)
+            dt, cls = float("nan"), None
     npairs = len(work.pairs)
-    value = npairs * steps1 / dt if weak_error is None else None
-    ms_per_step = dt / steps1 * 1e3 if weak_error is None else None
+    value = npairs * steps1 / dt if (first_leg and weak_error is None) else None
+    ms_per_step = dt / steps1 * 1e3 if (first_leg and weak_error is None) else None
+
+    # ---- what the timed path returned in its last step, before anything else touches the alm buffers ----------------
+    if args.dump_outputs and rank == 0 and world == 1:
+        dump = {"cl": cl_for_dump(cls)}
+        for name, a_, n_, seed in (("alm_spin0_sample", alm0, n0, 2), ("alm_spin2_sample", alm2, n2, 3)):
+            if n_:
+                flat = a_.view(-1)  # (rows of one contiguous buffer: a view, never a copy)
+                idx = torch.from_numpy(sample_index(flat.numel(), DUMP_ALM_SAMPLE, seed)).to(dev)
+                dump[name] = torch.view_as_real(flat.index_select(0, idx)).cpu().numpy()  # (k, 2): real, imaginary part
+        dump_outputs(args.dump_outputs, dump)
 
     # ---- per-family kernel times (HIP events on the library stream) ----------------------------------------------
     prof = {}
-    for k in ("ring_fft", "fourier_combine", "legendre_analysis", "legendre_analysis_s0", "legendre_analysis_s2",
-              "alm_reduce", "alm2cl"):
-        n_, ms_ = hx._lib.profile_get(k)
-        prof[k] = {"launches": n_, "ms_per_step": ms_ / max(steps1, 1)}
+    if first_leg:
+        for k in ("ring_fft", "fourier_combine", "legendre_analysis", "legendre_analysis_s0", "legendre_analysis_s2",
+                  "alm_reduce", "alm2cl"):
+            n_, ms_ = hx._lib.profile_get(k)
+            prof[k] = {"launches": n_, "ms_per_step": ms_ / max(steps1, 1)}
 
     # ---- roofline of the dominant kernel family (Legendre / Wigner-d analysis, FP64 MFMA + the vector recursion) ----
     F0 = 8.0 * 2 * nside * nlm  # ALGORITHMIC flops of one spin-0 component; a spin-2 field is 3 F0
@@ -485,8 +542,9 @@ def main():
         fn()
         return hx._lib.executed_flops(reset=True)
 
-    exec2 = counted(lambda: plan.map2alm(maps2.view(2 * n2, npix), 2, pix_weights=pw, out=alm2.view(2 * n2, nlm))) if n2 else (0.0, 0.0)
-    exec0 = counted(lambda: plan.map2alm(maps0, 0, pix_weights=pw, out=alm0)) if n0 else (0.0, 0.0)
+    if args.full:
+        exec2 = counted(lambda: plan.map2alm(maps2.view(2 * n2, npix), 2, pix_weights=pw, out=alm2.view(2 * n2, nlm))) if n2 else (0.0, 0.0)
+        exec0 = counted(lambda: plan.map2alm(maps0, 0, pix_weights=pw, out=alm0)) if n0 else (0.0, 0.0)
 
     def roof(name, kernel, alg_flops_step, spin, ncomp):
         nl_, ms_ = hx._lib.profile_get(name)
@@ -516,17 +574,21 @@ def main():
 
     nc0, nc2 = n0, 2 * n2
     # (at N > 1 the roofline blocks come from the first leg, whose per-GPU job is the N = 1 job: the same launches of the same kernels)
-    roofline = roof("legendre_analysis_s2", "hx::k_legendre_duo<2,*>", n2 * 3 * F0, 2, nc2)
-    roofline_s0 = roof("legendre_analysis_s0", "hx::k_legendre_duo<0,*>", n0 * F0, 0, nc0)
+    roofline, roofline_s0 = None, None
+    if args.full:
+        roofline = roof("legendre_analysis_s2", "hx::k_legendre_duo<2,*>", n2 * 3 * F0, 2, nc2)
+        roofline_s0 = roof("legendre_analysis_s0", "hx::k_legendre_duo<0,*>", n0 * F0, 0, nc0)
 
     # ---- N > 1: the FIXED job (one set of maps: the N = 1 job) on all N GPUs through both routes, K steps each.  `value` is the
     # better one: the same 210 pairs at every N. ----
+    # (with --scaling weak the routes are side figures: --full only)
     strong, verify_multi, routes, weak_check = None, None, None, None
-    if world > 1:
+    if world > 1 and (args.scaling == "strong" or args.full):
         if rank == 0 and not args.no_verify and cls is not None:
             e_, n_ = cl_direct_check(work, cls, [(0, 0), (0, nmaps_total - 1), (nmaps_total - 1, nmaps_total - 1), (0, nbins)])
             weak_check = {"max_err_over_max": e_, "spectra_checked": n_, "tolerance": 1e-11, "ok": bool(e_ <= 1e-11)}
-        del maps0, maps2, alm0, alm2  # (the weak-scaling job is done: room for the fixed job's buffers)
+        if first_leg:
+            del maps0, maps2, alm0, alm2  # (the weak-scaling job is done: room for the fixed job's buffers)
         work._buf = None
         torch.cuda.empty_cache()
         plan.release_scratch()  # (the full-size sweeps of the first leg hold ~100 GB of operands and rows; the routes below size their own)
@@ -642,6 +704,12 @@ def main():
         torch.cuda.empty_cache()
         best = max((k for k in routes if routes[k].get("value")), key=lambda k: routes[k]["value"], default=None)
         strong = dict(routes[best], route=best) if best else {"value": None, "error": "both fixed-job routes failed", "route": None}
+    if args.dump_outputs and rank == 0 and world > 1:
+        # the Cl rows of the job `value` is quoted on: the better route of the fixed job, or the growing job with --scaling weak
+        got = cls if args.scaling == "weak" else {"all_gather": rows, "m_sharded": cls_m}.get(strong.get("route"))
+        if got is None:
+            raise SystemExit("--dump-outputs: the timed job produced no Cl rows")
+        dump_outputs(args.dump_outputs, {"cl": cl_for_dump(np.asarray(got))})
 
     # ---- the mixing-matrix request list of BASELINE configs[4] (13 bins x (Positions on the visibility mask, Shears and a scalar on the
     # weight mask): 780 keys) with the configuration file's bins (32 log 2l+1, examples/heracles.cfg:4-6) -- the loop of
@@ -694,7 +762,7 @@ def main():
 
     out = None
     if rank == 0:
-        assert weak_error is not None or (cls is not None and cls.shape[0] == work.nrows)
+        assert not first_leg or weak_error is not None or (cls is not None and cls.shape[0] == work.nrows)
         # ---- host -> host leg (SURVEY 8d's metric definition: pageable numpy maps in, Cl blocks on the host out) -------
         # (before the CPU legs, so that their working set on the host is not in its way)
         host_leg = None
@@ -955,13 +1023,13 @@ def main():
                                      "(heracles/twopoint.py:391-397), numerators = (binned Wigner-d tables) diag(w xi) (tables)^T on the matrix unit, host -> host "
                                      "(cl on the host in, (3, bins, L + 1) numpy array out), median of 7; the reference bins the full matrix on the host "
                                      "column by column; host_binning_of_a_full_matrix_seconds is THIS repository's vectorised host rule on the same matrix"}
-        peaks = hx._lib.measure_peaks()
+        peaks = hx._lib.measure_peaks() if args.full else None
         ncomp_set = sum(2 if s_ else 1 for s_ in per_set)
         set_name = f"{nbins} bins x ({'2 spin-0 + 1 spin-2' if args.workload == 'euclid' else 'spin-0, spin-2'}) maps"
         common = (f"nside={nside}, lmax={lmax}, niter=0, ring weights 1, pix_weights: synthetic file in healpy's format (its files are not "
                   f"available offline); inputs resident in HBM")
         weak = None
-        if world > 1:
+        if world > 1 and first_leg:
             # the job that grows with N: every rank brings one set of maps; pairs grow as N^2 while the transforms per GPU stay what they are,
             # so its pairs/s is NOT a speed-up -- the per-GPU transform rate beside it is the weak-scaling figure proper
             weak = {"value": value, "unit": "map->Cl pairs/s", "ms_per_step": ms_per_step, "steps": steps1, "maps_total": nmaps_total,

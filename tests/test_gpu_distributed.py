@@ -190,7 +190,7 @@ def test_bench_rehearsal_two_ranks_verifies_itself(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--nside", "128", "--lmax", "160", "--nbins", "3", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
+           "--nside", "128", "--lmax", "160", "--nbins", "3", "--full", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -221,7 +221,7 @@ def test_bench_under_torchrun_still_works(tmp_path):
     env = dict(os.environ, HX_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--nside", "64", "--lmax", "96", "--nbins", "2", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
+           "--nside", "64", "--lmax", "96", "--nbins", "2", "--full", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -242,7 +242,7 @@ def test_bench_line_survives_a_failure_of_the_growing_job(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--nside", "64", "--lmax", "96", "--nbins", "2", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
+           "--nside", "64", "--lmax", "96", "--nbins", "2", "--full", "--no-cpu-baseline", "--no-mixmat", "--no-single", "--no-host-leg"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

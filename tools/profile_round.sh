@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-host-leg"
+LEAN="--full --no-cpu-baseline --no-host-leg"
 # 1. kernel trace + stats of the default bench command (no CPU-baseline / host legs: they are host code)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --steps 2 --warmup 1 $LEAN > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace done"

@@ -31,7 +31,7 @@ bench = open(f"{src}/bench_trace.json").read().strip().splitlines()[-1]
 open(f"profiles/{tag}_bench_under_rocprof.json", "w").write(bench + "\n")
 
 # 2. counters (smaller workload, one pass per counter group)
-out = [f"# PMC summary ({tag}): per-dispatch averages at FULL size (bench.py --steps 1 --warmup 0: nside 4096, lmax 6144, 10 + 10 maps)\n",
+out = [f"# PMC summary ({tag}): per-dispatch averages at FULL size (bench.py --full --steps 1 --warmup 0: nside 4096, lmax 6144, 10 + 10 maps)\n",
        "clock = GRBM_GUI_ACTIVE / 8 XCDs / duration; MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x duration x clock)\n"]
 for d in ("pmc_sq", "pmc_lds", "pmc_fetch", "pmc_write"):
     fs = sorted(glob.glob(f"{src}/{d}/*/*_counter_collection.csv"), key=os.path.getmtime, reverse=True)
@@ -85,7 +85,7 @@ for k, v in sorted(res.items()):
              "hbm_bytes_per_launch": (2 * fk / nf + wk / nw) * 1024}
 if tr:
     json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes, tools/profile_round.sh) of "
-                         "`bench.py --steps 1 --warmup 0` at nside 4096 / lmax 6144; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB: "
+                         "`bench.py --full --steps 1 --warmup 0` at nside 4096 / lmax 6144; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB: "
                          "FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950", "kernels": tr},
               open(f"profiles/{tag}_traffic.json", "w"), indent=1)
 print("wrote profiles/", tag)

@@ -34,6 +34,6 @@ for k, v in sorted(res.items()):
               "hbm_bytes_per_launch": (2 * fk / nf + wk / nw) * 1024}
     print(f"{k:40s} launches {nf:3d}  fetch(x2) {2 * fk / nf / 1e6:9.2f} GB  write {wk / nw / 1e6:9.2f} GB")
 json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes, tools/pmc_traffic.sh) of "
-                     "`bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-mixmat` at nside 4096 / lmax 6144; bytes = "
+                     "`bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-mixmat` at nside 4096 / lmax 6144; bytes = "
                      "(2 x FETCH_SIZE + WRITE_SIZE) KB: FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950",
            "kernels": out}, open(f"profiles/{tag}_traffic.json", "w"), indent=1)
