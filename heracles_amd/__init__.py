@@ -8,6 +8,20 @@ include/hxsht.h).  There is no CPU fallback.
 from . import _lib
 from ._lib import HxError, device_count, init, pinned_empty, release_caches, synchronize
 from .binning import BinPlan, binned
+from .covariance import (
+    bias,
+    debias_covariance,
+    delete2_correction,
+    flatten,
+    gaussian_covariance,
+    get_cl,
+    impose_correlation,
+    jackknife_bias,
+    jackknife_covariance,
+    sample_covariance,
+    shrink,
+    shrinkage_factor,
+)
 from .core import DeviceArray, Result, TocDict, toc_match, update_metadata
 from .discrete import HipDiscreteMapper, PointSHT, alm_resample, get_point_sht
 from .jackknife import RegionAlms, jackknife_cls, region_alms
@@ -39,4 +53,6 @@ __all__ = [
     "mixing_matrices", "mixmat", "mixmat_eb", "cl2corr", "corr2cl", "gauss_legendre",
     "wigner_d_table", "naturalspice", "Result", "TocDict", "toc_match", "update_metadata", "DeviceArray",
     "pinned_empty", "release_caches", "mixmat_release", "split_requests", "binned", "BinPlan", "MixmatContext", "jackknife_cls", "region_alms", "RegionAlms", "transform", "read_vmap", "apply_mixing_matrix", "invert_mixing_matrix",
+    "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
+    "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
 ]

@@ -32,6 +32,7 @@ SYMBOLS = (
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
     "hx_pixel_weights_size", "hx_pixel_weights_expand",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
+    "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
 )
 
 
@@ -137,6 +138,9 @@ def load():
         L.hx_host_free.argtypes = [vp]
         L.hx_mixmat_gemm_clock.restype = C.c_double
         L.hx_timer_stop.argtypes = [C.POINTER(C.c_float)]
+        L.hx_cov_gram.argtypes = [i, i, i, dp, dp, C.c_double, dp]
+        L.hx_cov_delete2.argtypes = [i, i, i, dp, dp, dp, vp, vp, i, vp, C.c_double, dp]
+        L.hx_cov_shrink_sums.argtypes = [i, i, dp, dp, C.c_int64, dp]
         L.hx_profile_get.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         _lib = L
         return L

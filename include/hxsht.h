@@ -307,6 +307,23 @@ int hx_reorder(int nside, int to_ring, int nmaps, const double *in, double *out)
 int64_t hx_pixel_weights_size(int nside);
 int hx_pixel_weights_expand(int nside, int64_t ncompressed, const double *compressed, double *weights);
 
+/* ---- covariance estimators of DICES (heracles/dices/jackknife.py:449-593, heracles/dices/shrinkage.py:66-98) ---------------------
+ * Samples are stacked one per row in data-vector order; every array is row-major, host or device.  Columns are centred in two
+ * passes, then every product runs on the FP64 matrix unit with K = the sample count; reductions in a fixed order (bitwise repeatable).
+ *  hx_cov_gram:        out (n1 x n2) = alpha Dx^T Dy, Dx / Dy the centred columns of x (n x n1) / y (n x n2); y NULL: y = x (n2 is
+ *                      ignored, only tiles I <= J are computed and mirrored).  sample_covariance (jackknife.py:504-528) is alpha =
+ *                      1 / (n - 1); jackknife_covariance (:449-501) scales it by (njk - 1)^2 / njk (nd = 1) or the delete-2 factor.
+ *  hx_cov_delete2:     the ensemble of delete2_correction (jackknife.py:542-552), Q[k] = njk c0 - (njk - 1) (c1[pairs[2k]] +
+ *                      c1[pairs[2k + 1]]) + (njk - 2) c2[k] for c0 (N), c1 (njk x N), c2 (m x N); its columns reordered by perm
+ *                      (column p of the product = data column perm[p]; NULL: identity), centred, and the Grams alpha D_b^T D_b of the
+ *                      nb column slabs [bstart[b], bstart[b + 1]) written back to back into out (sum of the squared widths).
+ *  hx_cov_shrink_sums: out[0] / out[1] = numerator / denominator of the optimal shrinkage factor (shrinkage.py:66-98) of the samples
+ *                      x (n x N) against the target (N x N, leading dimension ldt); the W ensemble is never formed. */
+int hx_cov_gram(int n, int n1, int n2, const double *x, const double *y, double alpha, double *out);
+int hx_cov_delete2(int njk, int m, int N, const double *c0, const double *c1, const double *c2, const int *pairs, const int *perm,
+                   int nb, const int *bstart, double alpha, double *out);
+int hx_cov_shrink_sums(int n, int N, const double *x, const double *target, int64_t ldt, double *out);
+
 #ifdef __cplusplus
 }
 #endif
