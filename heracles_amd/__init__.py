@@ -26,7 +26,20 @@ from .core import DeviceArray, Result, TocDict, toc_match, update_metadata
 from .discrete import HipDiscreteMapper, PointSHT, alm_resample, get_point_sht
 from .jackknife import RegionAlms, jackknife_cls, region_alms
 from .mapper import HipHealpixMapper
-from .mapping import transform
+from .catalog import ArrayCatalog
+from .fields import (
+    ComplexField,
+    Ellipticities,
+    Field,
+    Positions,
+    ScalarField,
+    Shears,
+    Spin2Field,
+    Visibility,
+    Weights,
+    get_masks,
+)
+from .mapping import map_catalogs, transform
 from .sht import Plan, get_plan
 from .transforms import cl2corr, corr2cl, gauss_legendre, wigner_d_table
 from .fits import read_vmap
@@ -55,4 +68,6 @@ __all__ = [
     "pinned_empty", "release_caches", "mixmat_release", "split_requests", "binned", "BinPlan", "MixmatContext", "jackknife_cls", "region_alms", "RegionAlms", "transform", "read_vmap", "apply_mixing_matrix", "invert_mixing_matrix",
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
+    "map_catalogs", "ArrayCatalog", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
+    "Visibility", "Weights", "get_masks",
 ]

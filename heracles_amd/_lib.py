@@ -33,6 +33,7 @@ SYMBOLS = (
     "hx_pixel_weights_size", "hx_pixel_weights_expand",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
+    "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
 )
 
 
@@ -141,6 +142,13 @@ def load():
         L.hx_cov_gram.argtypes = [i, i, i, dp, dp, C.c_double, dp]
         L.hx_cov_delete2.argtypes = [i, i, i, dp, dp, dp, vp, vp, i, vp, C.c_double, dp]
         L.hx_cov_shrink_sums.argtypes = [i, i, dp, dp, C.c_int64, dp]
+        L.hx_catmap_create.restype = vp
+        L.hx_catmap_create.argtypes = [C.c_int64, i, i, vp, vp]
+        L.hx_catmap_page.argtypes = [vp, C.c_int64, vp]
+        L.hx_catmap_moments.argtypes = [vp, dp, dp]
+        L.hx_catmap_finish.argtypes = [vp, i, C.c_double, dp]
+        L.hx_catmap_destroy.argtypes = [vp]
+        L.hx_catmap_destroy.restype = None
         L.hx_profile_get.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         _lib = L
         return L

@@ -262,6 +262,10 @@ class HipHealpixMapper:
         if self.pixel_weights is None and self.ring_weights is None:
             _warn_unit_weights()
         plan = sht.get_plan(self.__nside, self.__lmax)
+        if isinstance(data, DeviceArray):
+            # a device map with metadata (map_catalogs(device=...)): the alm stays in HBM and carries it on
+            alm = self.transform(data.tensor, spin)
+            return DeviceArray(alm, {**(data.dtype.metadata or {}), "deconv": self.__deconv})
         if hasattr(data, "data_ptr"):
             # device-resident maps (e.g. accumulated by map_values on the GPU): alms stay in HBM; a torch
             # tensor cannot carry dtype metadata, so none is attached
@@ -291,7 +295,9 @@ class HipHealpixMapper:
             _warn_unit_weights()
         plan = sht.get_plan(self.__nside, self.__lmax)
         npix, nlm = 12 * self.__nside**2, (self.__lmax + 1) * (self.__lmax + 2) // 2
-        native = [m if hasattr(m, "data_ptr") else np.ascontiguousarray(_native(m), dtype=np.float64) for m in maps]
+        # a DeviceArray map (map_catalogs(device=...)) goes in as its tensor and hands its metadata on to the alm
+        native = [m.tensor if isinstance(m, DeviceArray) else m if hasattr(m, "data_ptr")
+                  else np.ascontiguousarray(_native(m), dtype=np.float64) for m in maps]
         native = [m.reshape((npix,) if sp == 0 else (2, npix)) for m, sp in zip(native, spins)]
         outs = None
         if device is not None:
@@ -302,8 +308,8 @@ class HipHealpixMapper:
                                  fl0=self._fl(0), fl2=self._fl(2), niter=self.niter)
         out = []
         for m, a, sp in zip(maps, alms, spins):
-            md = {**((m.dtype.metadata or {}) if isinstance(m, np.ndarray) else {"spin": sp}), "deconv": self.__deconv}
-            if device is not None:
+            md = {**((m.dtype.metadata or {}) if isinstance(m, (np.ndarray, DeviceArray)) else {"spin": sp}), "deconv": self.__deconv}
+            if device is not None or isinstance(m, DeviceArray):
                 out.append(DeviceArray(a, md))
                 continue
             if hasattr(a, "data_ptr"):

@@ -300,6 +300,37 @@ int hx_ud_grade(int nside_in, int nside_out, int nmaps, const double *in, double
  * not in place.  nside a power of two.                                                                              */
 int hx_reorder(int nside, int to_ring, int nmaps, const double *in, double *out);
 
+/* ---- catalogues -> field maps: heracles.map_catalogs with the fields of heracles/fields.py:197-559 -----------------
+ * One context maps the pages of ONE catalogue into the maps of up to HX_CAT_MAX_FIELDS fields at once.  desc holds 7 ints per field:
+ * {kind, nside, lon, lat, value (real part), imag, weight}, the last five indices into the column list every page passes (-1 = none;
+ * a field without a weight column uses w = 1).  maps[f]: the field's DEVICE map, zeroed by the caller, [nrow][12 nside^2] with
+ * nrow = 2 for HX_CAT_COMPLEX, else 1.  Fields that share (nside, lon, lat) share one ang2pix and one stable pixel sort per page.
+ *  kinds:  POSITIONS adds w and keeps every row; SCALAR adds w v, COMPLEX w re and w im, WEIGHTS w, and these three drop the rows with
+ *          w == 0 before anything else (their values and positions are neither checked nor added).  Products round one by one (no FMA).
+ *  hx_catmap_page:    adds one page of n <= page_size rows; cols: the page's columns, host or device.  Host columns are uploaded on the
+ *                     library's copy stream into one of two staging sets, so the upload of the next page overlaps this page's kernels;
+ *                     the call returns once the host columns have been read (device columns: once the page is mapped).  Per pixel the
+ *                     rows add in catalogue order: bit-identical to the reference's _map loop (heracles/healpy.py:58-66).
+ *  hx_catmap_moments: waits for the pages, then out[4 f + k] = {n, sum w, sum w^2, sum |w v|^2} of the rows field f kept (summed per
+ *                     block, then over blocks in a fixed order: bitwise repeatable) and bad[6 f + k] = the kept rows with a NaN in
+ *                     {lon, lat, value, imag, weight} (k < 5) and those with an invalid position (k = 5: latitude outside [-90, 90] or a
+ *                     non-finite coordinate; such rows are never added).  The caller raises on either count; the maps are then void.
+ *  hx_catmap_finish:  map <- map / norm - vis (each operation rounded on its own; vis NULL: map / norm), in place.  vis: [12 nside^2],
+ *                     host or device.                                                                                             */
+typedef struct hx_catmap hx_catmap;
+#define HX_CAT_POSITIONS 0
+#define HX_CAT_SCALAR 1
+#define HX_CAT_COMPLEX 2
+#define HX_CAT_WEIGHTS 3
+#define HX_CAT_MAX_FIELDS 8
+#define HX_CAT_MAX_GROUPS 4
+#define HX_CAT_MAX_COLUMNS 16
+hx_catmap *hx_catmap_create(int64_t page_size, int ncols, int nfields, const int *desc, double *const *maps);
+int hx_catmap_page(hx_catmap *ctx, int64_t n, const double *const *cols);
+int hx_catmap_moments(hx_catmap *ctx, double *out, int64_t *bad);
+int hx_catmap_finish(hx_catmap *ctx, int field, double norm, const double *vis);
+void hx_catmap_destroy(hx_catmap *ctx);
+
 /* healpy's pixel-weight files (`healpix_full_weights_nside_NNNN.fits`, the data hp.map2alm(use_pixel_weights=True, datapath=...)
  * of heracles/healpy.py:183-189 reads): expansion of the compressed half-quadrant weights -- hx_pixel_weights_size(nside) =
  * (nside + 1)(3 nside + 1) / 4 values -- to the full-sky array [12 nside^2] of multiplicative pixel weights 1 + w that hx_map2alm
