@@ -902,3 +902,581 @@ extern "C" int hx_catmap_finish(hx_catmap *c, int field, double norm, const doub
     HX_HIP(hipStreamSynchronize(rt().stream));  // (a staged visibility dies with this scope)
     return HX_OK;
 }
+
+// =====================================================================================
+// selections: the views of one base catalogue (heracles/catalog/base.py:204-310) mapped in one pass over the base's pages
+// =====================================================================================
+// Nothing in a page's mapping depends on the selection but the sort key: the value rows w v and the pixel of a row are the same for every
+// view.  k_sel_prepare therefore reads the page once: it forms each row's membership word (bit s: the base's filters keep the row, its
+// mask word has bit s, and every predicate term of selection s holds), writes the value rows and the pixels of every group as
+// k_cat_prepare does, and sums the moments of every (selection, field): a ballot loop over the selections present in the wave, the wave
+// sums kept per wave in LDS (one writer each), the four waves and then the blocks added in a fixed order.  k_sel_keys turns (membership,
+// pixel) into the key s (npix + 1) + pixel, npix being the sentinel of the selection's unkept rows and nsel (npix + 1) that of rows in no
+// selection; a row in k > 1 selections gets k keys at offsets from an exclusive scan of the per-row key counts (only when some row of the
+// page has k > 1: disjoint selections sort n keys).  One stable sort per group orders them, and k_sel_run_add adds each run into the
+// map of its key's selection, in catalogue order.
+namespace hx {
+namespace {
+
+constexpr int kSelS = HX_CAT_MAX_SELECTIONS, kSelP = HX_CAT_MAX_PREDICATES, kSelFl = HX_CAT_MAX_FILTERS;
+
+struct SelArgs {
+    const double *col[kCatC];
+    const unsigned *mask;  // per row, or null (every bit set)
+    unsigned *pix[kCatG];  // per group: the row's pixel, npix for a row no field of the group keeps or an invalid position
+    int gnside[kCatG], glon[kCatG], glat[kCatG];
+    double *val[kCatF];
+    int kind[kCatF], grp[kCatF], cv[kCatF], ci[kCatF], cw[kCatF];
+    int nfield, ngroup, nsel, npred, nfilt;
+    long long cap;
+    int pmeta[kSelP];  // selection | column << 8 | op << 16
+    double pval[kSelP];
+    int ftype[kSelFl], fa[kSelFl], fb[kSelFl], fnside[kSelFl];
+    const double *fp[kSelFl];
+    unsigned *mem;                // [n] membership words
+    unsigned *cnt;                // [n] keys per row: max(1, popcount)
+    unsigned long long *nan;      // [nsel][nfield][5]
+    unsigned long long *nbad;     // [nsel][ngroup]
+    unsigned long long *fcount;   // [nsel][nfilt + 1]
+    unsigned long long *extra;    // sum over rows of popcount - 1
+    double *slab;                 // [gridDim.x][nsel nfield 4]
+};
+
+__device__ inline bool sel_compare(double x, int op, double c)
+{
+    switch (op) {
+    case HX_CAT_EQ: return x == c;
+    case HX_CAT_NE: return x != c;
+    case HX_CAT_LT: return x < c;
+    case HX_CAT_LE: return x <= c;
+    case HX_CAT_GT: return x > c;
+    default: return x >= c;
+    }
+}
+
+// add 1 to cnt[s * stride + k] for every bit s of m (rare events: NaNs, invalid positions, filtered rows)
+__device__ inline void count_bits(unsigned m, unsigned long long *cnt, int stride, int k)
+{
+    while (m) {
+        const int s = __ffs(m) - 1;
+        m &= m - 1;
+        atomicAdd(cnt + (long long)s * stride + k, 1ULL);
+    }
+}
+
+template <int NF>
+__global__ __launch_bounds__(256) void k_sel_prepare(long long n, SelArgs a)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double wpart[];  // [4 waves][nsel NF 4]
+    const int W = a.nsel * NF * 4, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int t = threadIdx.x; t < 4 * W; t += blockDim.x) wpart[t] = 0.0;
+    __syncthreads();
+    double *mine = wpart + wv * W;
+    const unsigned all = a.nsel == 32 ? ~0u : (1u << a.nsel) - 1u;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    // the loop bound is uniform over the block: the ballots below need every lane of the wave
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += stride) {
+        const long long j = base + threadIdx.x;
+        const bool active = j < n;
+        unsigned m = 0;
+        double c[NF][4];
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[f][k] = 0.0;
+        if (active) {
+            m = (a.mask ? a.mask[j] : ~0u) & all;
+            for (int p = 0; p < a.npred; ++p) {
+                const int meta = a.pmeta[p];
+                if (!sel_compare(a.col[(meta >> 8) & 255][j], meta >> 16, a.pval[p])) m &= ~(1u << (meta & 255));
+            }
+            // the base's filters, in order, on the rows some selection holds (a view selects before it filters)
+            for (int k = 0; m && k < a.nfilt; ++k) {
+                bool drop = false;
+                if (a.ftype[k] == HX_CAT_FILTER_INVALID) {
+                    for (int cc = 0; cc < kCatC; ++cc)
+                        if ((a.fa[k] >> cc) & 1) drop = drop || isnan(a.col[cc][j]);
+                    if (drop && a.fb[k] >= 0) drop = a.col[a.fb[k]][j] != 0.0;
+                } else {
+                    const double lo = a.col[a.fa[k]][j], la = a.col[a.fb[k]][j];
+                    const long long ns = a.fnside[k], np = 12 * ns * ns;
+                    const long long q = lonlat_valid(lo, la) ? ang2pix_ring_one(ns, lo, la) : -1;
+                    if (q < 0 || q >= np) {
+                        count_bits(m, a.fcount, a.nfilt + 1, a.nfilt);
+                        drop = true;
+                    } else {
+                        drop = a.fp[k][q] == 0.0;
+                    }
+                }
+                if (drop) {
+                    count_bits(m, a.fcount, a.nfilt + 1, k);
+                    m = 0;
+                }
+            }
+        }
+        bool keep_g[kCatG];
+#pragma unroll
+        for (int g = 0; g < kCatG; ++g) keep_g[g] = false;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            if (!active) continue;
+            const int kind = a.kind[f];
+            const double w = a.cw[f] >= 0 ? a.col[a.cw[f]][j] : 1.0;
+            const bool keep = kind == HX_CAT_POSITIONS || w != 0.0;
+            double r0 = 0.0, r1 = 0.0;
+            if (keep) {
+#pragma unroll
+                for (int g = 0; g < kCatG; ++g)
+                    if (g == a.grp[f]) keep_g[g] = true;
+                const int g = a.grp[f];
+                unsigned long long *nan = a.nan + 5 * f;
+                const int ns5 = 5 * a.nfield;
+                if (m && isnan(a.col[a.glon[g]][j])) count_bits(m, nan, ns5, 0);
+                if (m && isnan(a.col[a.glat[g]][j])) count_bits(m, nan, ns5, 1);
+                if (m && isnan(w)) count_bits(m, nan, ns5, 4);
+                if (kind == HX_CAT_SCALAR || kind == HX_CAT_COMPLEX) {
+                    const double v = a.col[a.cv[f]][j];
+                    if (m && isnan(v)) count_bits(m, nan, ns5, 2);
+                    r0 = v * w;
+                    if (kind == HX_CAT_COMPLEX) {
+                        const double im = a.col[a.ci[f]][j];
+                        if (m && isnan(im)) count_bits(m, nan, ns5, 3);
+                        r1 = im * w;
+                    }
+                    c[f][3] = r0 * r0 + r1 * r1;
+                } else {
+                    r0 = w;
+                }
+                c[f][0] = 1.0;
+                c[f][1] = w;
+                c[f][2] = w * w;
+            }
+            a.val[f][j] = r0;
+            if (kind == HX_CAT_COMPLEX) a.val[f][a.cap + j] = r1;
+        }
+        if (active) {
+#pragma unroll
+            for (int g = 0; g < kCatG; ++g) {
+                if (g >= a.ngroup) break;
+                const long long nside = a.gnside[g], npix = 12 * nside * nside;
+                long long p = npix;
+                if (m && keep_g[g]) {
+                    const double lo = a.col[a.glon[g]][j], la = a.col[a.glat[g]][j];
+                    const long long q = lonlat_valid(lo, la) ? ang2pix_ring_one(nside, lo, la) : -1;
+                    if (q < 0 || q >= npix) count_bits(m, a.nbad, a.ngroup, g);
+                    else p = q;
+                }
+                a.pix[g][j] = (unsigned)p;
+            }
+            const int pc = __popc(m);
+            a.mem[j] = m;
+            a.cnt[j] = pc > 1 ? (unsigned)pc : 1u;
+        }
+        // rows in more than one selection: one atomic per wave
+        unsigned ex = __popc(m) > 1 ? (unsigned)__popc(m) - 1u : 0u;
+        unsigned orm = m;
+        for (int off = 32; off > 0; off >>= 1) {
+            ex += __shfl_xor(ex, off, 64);
+            orm |= __shfl_xor(orm, off, 64);
+        }
+        if (lane == 0 && ex) atomicAdd(a.extra, (unsigned long long)ex);
+        // moments: for every selection present in the wave, the wave sums of its rows' contributions (fixed shape, one writer)
+        while (orm) {
+            const int s = __ffs(orm) - 1;
+            orm &= orm - 1;
+            const bool in = (m >> s) & 1u;
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double t = wave_sum(in ? c[f][k] : 0.0);
+                    if (lane == 0) mine[(s * NF + f) * 4 + k] += t;
+                }
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < W; t += blockDim.x)
+        a.slab[(long long)blockIdx.x * W + t] = ((wpart[t] + wpart[W + t]) + wpart[2 * W + t]) + wpart[3 * W + t];
+}
+
+// acc[t] += sum over blocks of slab[b][t], b in order
+__global__ __launch_bounds__(256) void k_sel_reduce(int nblocks, int width, const double *__restrict__ slab, double *__restrict__ acc)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= width) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s += slab[(long long)b * width + t];
+    acc[t] += s;
+}
+
+// the keys of row j at off[j] (or j when no row has more than one): s (npix + 1) + pixel for every bit s, in ascending s
+__global__ __launch_bounds__(256) void k_sel_keys(long long n, const unsigned *__restrict__ mem, const unsigned *__restrict__ off,
+                                                  const unsigned *__restrict__ pix, long long npix1, int nsel, long long *__restrict__ key,
+                                                  unsigned *__restrict__ ord)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    unsigned m = mem[j];
+    long long o = off ? (long long)off[j] : j;
+    if (!m) {
+        key[o] = (long long)nsel * npix1;
+        ord[o] = (unsigned)j;
+        return;
+    }
+    const long long p = pix[j];
+    while (m) {
+        const int s = __ffs(m) - 1;
+        m &= m - 1;
+        key[o] = (long long)s * npix1 + p;
+        ord[o] = (unsigned)j;
+        ++o;
+    }
+}
+
+// k_cat_run_add for one value row and the map rows of every selection: the run's key names its selection and pixel
+template <class K>
+__global__ __launch_bounds__(256) void k_sel_run_add(long long n, const K *__restrict__ keys, const unsigned *__restrict__ idx_sorted,
+                                                     long long npix1, int nsel, const double *__restrict__ vrow,
+                                                     double *const *__restrict__ mrows)
+{
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const K k = keys[s];
+    if (s > 0 && keys[s - 1] == k) return;
+    const long long sel = (long long)k / npix1, p = (long long)k - sel * npix1;
+    if (sel >= nsel || p == npix1 - 1) return;
+    long long e = s + 1;
+    while (e < n && keys[e] == k) ++e;
+    double *map = mrows[sel];
+    double acc = map[p];
+    for (long long t = s; t < e; ++t) acc += vrow[idx_sorted[t]];
+    map[p] = acc;
+}
+
+}  // namespace
+}  // namespace hx
+
+struct hx_catmap_sel {
+    long long cap = 0;
+    int ncols = 0, nfield = 0, ngroup = 0, nsel = 0, nfilt = 0;
+    int kind[kCatF] = {}, grp[kCatF] = {}, nside[kCatF] = {}, nrow[kCatF] = {};
+    double *map[kSelS * kCatF] = {};
+    SelArgs args{};
+    DevBuf mrows[kCatF];  // per field: for each of its rows, the nsel map-row pointers
+    DevBuf val[kCatF], pix[kCatG], mem, cnt, scan_sums, key, key2, ord, ka, kb, v1, sort_tmp;
+    DevBuf stage[2][kCatC + 1];  // the columns, then the mask words
+    DevBuf slab, acc, counters;  // counters: nan [nsel][nfield][5], nbad [nsel][ngroup], fcount [nsel][nfilt + 1], extra
+    hipEvent_t ev_up[2] = {}, ev_done[2] = {};
+    long long page_no = 0;
+    ~hx_catmap_sel()
+    {
+        (void)hipStreamSynchronize(rt().stream);
+        for (int s = 0; s < 2; ++s) {
+            if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
+            if (ev_done[s]) (void)hipEventDestroy(ev_done[s]);
+        }
+    }
+    size_t n_nan() const { return (size_t)nsel * nfield * 5; }
+    size_t n_bad() const { return (size_t)nsel * ngroup; }
+    size_t n_fcount() const { return (size_t)nsel * (nfilt + 1); }
+};
+
+static int catmap_sel_init(hx_catmap_sel *c, int64_t page_size, int ncols, int nfields, const int *desc, int nsel, int npred,
+                           const int *preds, const double *pval, int nfilt, const int *filters, const double *const *footprints,
+                           double *const *maps)
+{
+    if (page_size < 1 || page_size > 0xfffffff0ll || ncols < 2 || ncols > kCatC || nfields < 1 || nfields > kCatF || !desc || !maps ||
+        nsel < 1 || nsel > kSelS || npred < 0 || npred > kSelP || (npred && (!preds || !pval)) || nfilt < 0 || nfilt > kSelFl ||
+        (nfilt && !filters))
+        return fail(HX_ERR_ARG, "hx_catmap_create_sel: bad arguments (page_size=%lld ncols=%d nfields=%d nsel=%d npred=%d nfilt=%d; at most "
+                    "%d columns, %d fields, %d selections, %d predicates and %d filters)", (long long)page_size, ncols, nfields, nsel,
+                    npred, nfilt, kCatC, kCatF, kSelS, kSelP, kSelFl);
+    c->cap = page_size;
+    c->ncols = ncols;
+    c->nfield = nfields;
+    c->nsel = nsel;
+    c->nfilt = nfilt;
+    SelArgs &a = c->args;
+    a.cap = page_size;
+    a.nfield = nfields;
+    a.nsel = nsel;
+    a.npred = npred;
+    a.nfilt = nfilt;
+    auto colok = [&](int i, bool need) { return need ? (i >= 0 && i < ncols) : (i >= -1 && i < ncols); };
+    for (int p = 0; p < npred; ++p) {
+        const int s = preds[3 * p], col = preds[3 * p + 1], op = preds[3 * p + 2];
+        if (s < 0 || s >= nsel || !colok(col, true) || op < HX_CAT_EQ || op > HX_CAT_GE)
+            return fail(HX_ERR_ARG, "hx_catmap_create_sel: bad predicate %d (selection %d, column %d, op %d)", p, s, col, op);
+        a.pmeta[p] = s | col << 8 | op << 16;
+        a.pval[p] = pval[p];
+    }
+    for (int k = 0; k < nfilt; ++k) {
+        const int *d = filters + 4 * k;
+        bool ok;
+        if (d[0] == HX_CAT_FILTER_INVALID) {
+            ok = d[1] != 0 && (unsigned)d[1] < (1u << ncols) && colok(d[2], false);
+        } else {
+            ok = d[0] == HX_CAT_FILTER_FOOTPRINT && colok(d[1], true) && colok(d[2], true) && nside_ok(d[3]) && d[3] <= 16384 && footprints &&
+                 footprints[k] && is_device_ptr(footprints[k]);
+            if (ok) a.fp[k] = footprints[k];
+        }
+        if (!ok)
+            return fail(HX_ERR_ARG, "hx_catmap_create_sel: bad filter %d (type %d; footprints must be device memory)", k, d[0]);
+        a.ftype[k] = d[0];
+        a.fa[k] = d[1];
+        a.fb[k] = d[2];
+        a.fnside[k] = d[3];
+    }
+    for (int f = 0; f < nfields; ++f) {
+        const int *d = desc + 7 * f;
+        const int kind = d[0], ns = d[1];
+        const bool need_v = kind == HX_CAT_SCALAR || kind == HX_CAT_COMPLEX;
+        bool maps_ok = true;
+        for (int s = 0; s < nsel; ++s) maps_ok = maps_ok && maps[s * nfields + f] && is_device_ptr(maps[s * nfields + f]);
+        if (kind < HX_CAT_POSITIONS || kind > HX_CAT_WEIGHTS || !nside_ok(ns) || ns > 16384 || !colok(d[2], true) || !colok(d[3], true) ||
+            !colok(d[4], need_v) || !colok(d[5], kind == HX_CAT_COMPLEX) || !colok(d[6], false) || !maps_ok)
+            return fail(HX_ERR_ARG, "hx_catmap_create_sel: bad descriptor of field %d (kind %d, nside %d; maps must be device memory)", f,
+                        kind, ns);
+        int g = 0;
+        for (; g < c->ngroup; ++g)
+            if (a.gnside[g] == ns && a.glon[g] == d[2] && a.glat[g] == d[3]) break;
+        if (g == c->ngroup) {
+            if (g == kCatG) return fail(HX_ERR_UNSUPPORTED, "hx_catmap_create_sel: more than %d (nside, lon, lat) groups", kCatG);
+            a.gnside[g] = ns;
+            a.glon[g] = d[2];
+            a.glat[g] = d[3];
+            ++c->ngroup;
+        }
+        c->kind[f] = a.kind[f] = kind;
+        c->grp[f] = a.grp[f] = g;
+        c->nside[f] = ns;
+        c->nrow[f] = kind == HX_CAT_COMPLEX ? 2 : 1;
+        a.cv[f] = d[4];
+        a.ci[f] = d[5];
+        a.cw[f] = d[6];
+        HX_TRY(c->val[f].alloc(sizeof(double) * page_size * c->nrow[f]));
+        a.val[f] = c->val[f].as<double>();
+        const long long npix = 12ll * ns * ns;
+        std::vector<double *> rows;
+        for (int r = 0; r < c->nrow[f]; ++r)
+            for (int s = 0; s < nsel; ++s) rows.push_back(maps[s * nfields + f] + r * npix);
+        for (int s = 0; s < nsel; ++s) c->map[s * nfields + f] = maps[s * nfields + f];
+        HX_TRY(c->mrows[f].alloc(sizeof(double *) * rows.size()));
+        HX_HIP(hipMemcpy(c->mrows[f].p, rows.data(), sizeof(double *) * rows.size(), hipMemcpyHostToDevice));
+    }
+    a.ngroup = c->ngroup;
+    for (int g = 0; g < c->ngroup; ++g) {
+        HX_TRY(c->pix[g].alloc(sizeof(unsigned) * page_size));
+        a.pix[g] = c->pix[g].as<unsigned>();
+    }
+    HX_TRY(c->mem.alloc(sizeof(unsigned) * page_size));
+    HX_TRY(c->cnt.alloc(sizeof(unsigned) * page_size));
+    a.mem = c->mem.as<unsigned>();
+    a.cnt = c->cnt.as<unsigned>();
+    const int width = nsel * nfields * 4;
+    HX_TRY(c->slab.alloc(sizeof(double) * kCatBlocks * width));
+    HX_TRY(c->acc.alloc(sizeof(double) * width));
+    HX_TRY(c->counters.alloc(sizeof(unsigned long long) * (c->n_nan() + c->n_bad() + c->n_fcount() + 1)));
+    hipStream_t st = rt().stream;
+    HX_HIP(hipMemsetAsync(c->acc.p, 0, c->acc.bytes, st));
+    HX_HIP(hipMemsetAsync(c->counters.p, 0, c->counters.bytes, st));
+    a.slab = c->slab.as<double>();
+    a.nan = c->counters.as<unsigned long long>();
+    a.nbad = a.nan + c->n_nan();
+    a.fcount = a.nbad + c->n_bad();
+    a.extra = a.fcount + c->n_fcount();
+    for (int s = 0; s < 2; ++s) {
+        HX_HIP(hipEventCreateWithFlags(&c->ev_up[s], hipEventDisableTiming));
+        HX_HIP(hipEventCreateWithFlags(&c->ev_done[s], hipEventDisableTiming));
+        HX_HIP(hipEventRecord(c->ev_done[s], st));
+    }
+    return HX_OK;
+}
+
+extern "C" hx_catmap_sel *hx_catmap_create_sel(int64_t page_size, int ncols, int nfields, const int *desc, int nsel, int npred,
+                                               const int *preds, const double *pval, int nfilt, const int *filters,
+                                               const double *const *footprints, double *const *maps)
+{
+    if (ensure_ready() != HX_OK) return nullptr;
+    hx_catmap_sel *c = new hx_catmap_sel;
+    if (catmap_sel_init(c, page_size, ncols, nfields, desc, nsel, npred, preds, pval, nfilt, filters, footprints, maps) != HX_OK) {
+        delete c;
+        return nullptr;
+    }
+    return c;
+}
+
+extern "C" void hx_catmap_destroy_sel(hx_catmap_sel *c) { delete c; }
+
+extern "C" int hx_catmap_page_sel(hx_catmap_sel *c, int64_t n, const double *const *cols, const uint32_t *mask)
+{
+    HX_TRY(ensure_ready());
+    if (!c || n < 0 || n > c->cap || (n > 0 && !cols))
+        return fail(HX_ERR_ARG, "hx_catmap_page_sel: bad arguments (n=%lld, page size %lld)", (long long)n, c ? c->cap : 0ll);
+    if (n == 0) return HX_OK;
+    for (int i = 0; i < c->ncols; ++i)
+        if (!cols[i]) return fail(HX_ERR_ARG, "hx_catmap_page_sel: column %d is NULL", i);
+    hipStream_t st = rt().stream, cs = copy_stream();
+    if (!cs) cs = st;
+    const int s = (int)(c->page_no++ & 1);
+    SelArgs a = c->args;
+    bool any_dev = false, uploaded = false, any_pinned = false;
+    HX_HIP(hipStreamWaitEvent(cs, c->ev_done[s], 0));
+    for (int i = 0; i <= c->ncols; ++i) {
+        const void *src = i < c->ncols ? (const void *)cols[i] : (const void *)mask;
+        const size_t elem = i < c->ncols ? sizeof(double) : sizeof(unsigned);
+        if (!src) continue;  // (no mask)
+        const void *dev = src;
+        if (is_device_ptr(src)) {
+            any_dev = true;
+        } else {
+            HX_TRY(c->stage[s][i].alloc(elem * c->cap));
+            any_pinned = any_pinned || is_pinned_host(src);
+            HX_TRY(copy_h2d(c->stage[s][i].p, src, elem * n, cs));
+            dev = c->stage[s][i].p;
+            uploaded = true;
+        }
+        if (i < c->ncols) a.col[i] = static_cast<const double *>(dev);
+        else a.mask = static_cast<const unsigned *>(dev);
+    }
+    if (!mask) a.mask = nullptr;
+    if (uploaded && cs != st) {
+        HX_HIP(hipEventRecord(c->ev_up[s], cs));
+        HX_HIP(hipStreamWaitEvent(st, c->ev_up[s], 0));
+    }
+    const unsigned nblocks = (unsigned)std::min<long long>((n + 255) / 256, kCatBlocks);
+    const int width = c->nsel * c->nfield * 4;
+    unsigned long long extra = 0;
+    {
+        ProfScope ps("catmap_prepare");
+        const size_t lds = sizeof(double) * 4 * width;
+        HX_HIP(hipMemsetAsync(a.extra, 0, sizeof(unsigned long long), st));
+        switch (c->nfield) {
+#define HX_SEL_PREP(NF) case NF: hipLaunchKernelGGL(k_sel_prepare<NF>, dim3(nblocks), dim3(256), lds, st, (long long)n, a); break;
+            HX_SEL_PREP(1) HX_SEL_PREP(2) HX_SEL_PREP(3) HX_SEL_PREP(4) HX_SEL_PREP(5) HX_SEL_PREP(6) HX_SEL_PREP(7) HX_SEL_PREP(8)
+#undef HX_SEL_PREP
+        }
+        hipLaunchKernelGGL(k_sel_reduce, dim3((width + 255) / 256), dim3(256), 0, st, (int)nblocks, width, c->slab.as<double>(),
+                           c->acc.as<double>());
+        HX_HIP(hipGetLastError());
+        // the number of keys decides the sort's size: rows in several selections enter it once per selection
+        HX_HIP(hipMemcpyAsync(&extra, a.extra, sizeof(extra), hipMemcpyDeviceToHost, st));
+        HX_HIP(hipStreamSynchronize(st));
+    }
+    const unsigned long long nkeys = (unsigned long long)n + extra;
+    if (nkeys > 0xfffffff0ull)
+        return fail(HX_ERR_UNSUPPORTED, "hx_catmap_page_sel: %llu (row, selection) pairs in one page (at most 2^32 - 16): use smaller pages",
+                    nkeys);
+    const unsigned *off = nullptr;
+    if (extra) {
+        // exclusive scan of the per-row key counts, in place
+        ProfScope ps("catmap_sort");
+        const unsigned long long e = (unsigned long long)n;
+        const unsigned nsb = (unsigned)((e + rsort::SCAN_TILE - 1) / rsort::SCAN_TILE);
+        HX_TRY(c->scan_sums.alloc(sizeof(unsigned) * (nsb + 16)));
+        hipLaunchKernelGGL(rsort::k_scan_sums, dim3(nsb), dim3(rsort::SCAN_T), 0, st, c->cnt.as<unsigned>(), e, c->scan_sums.as<unsigned>());
+        hipLaunchKernelGGL(rsort::k_scan_top, dim3(1), dim3(1024), 0, st, c->scan_sums.as<unsigned>(), nsb);
+        hipLaunchKernelGGL(rsort::k_scan_apply, dim3(nsb), dim3(rsort::SCAN_T), 0, st, c->cnt.as<unsigned>(), e, c->scan_sums.as<unsigned>());
+        HX_HIP(hipGetLastError());
+        off = c->cnt.as<unsigned>();
+    }
+    HX_TRY(c->key.alloc(sizeof(long long) * nkeys));
+    HX_TRY(c->ord.alloc(sizeof(unsigned) * nkeys));
+    HX_TRY(c->v1.alloc(sizeof(unsigned) * nkeys));
+    for (int g = 0; g < c->ngroup; ++g) {
+        const long long npix = 12ll * a.gnside[g] * a.gnside[g], npix1 = npix + 1;
+        const unsigned long long top = (unsigned long long)c->nsel * (unsigned long long)npix1;  // the largest key
+        int end_bit = 1;
+        while (end_bit < 64 && (1ull << end_bit) <= top) ++end_bit;
+        const unsigned *ks32 = nullptr;
+        const long long *ks64 = nullptr;
+        unsigned *vs = nullptr;
+        {
+            ProfScope ps("catmap_sort");
+            hipLaunchKernelGGL(k_sel_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, c->mem.as<unsigned>(), off,
+                               c->pix[g].as<unsigned>(), npix1, c->nsel, c->key.as<long long>(), c->ord.as<unsigned>());
+            HX_HIP(hipGetLastError());
+            if (end_bit <= 32) {
+                HX_TRY(c->ka.alloc(sizeof(unsigned) * nkeys));
+                HX_TRY(c->kb.alloc(sizeof(unsigned) * nkeys));
+                unsigned *k = nullptr;
+                HX_TRY(rsort::radix_sort_pairs_narrow(c->key.as<long long>(), c->ord.as<unsigned>(), c->ka.as<unsigned>(), c->kb.as<unsigned>(),
+                                                      c->v1.as<unsigned>(), nkeys, end_bit, c->sort_tmp, st, &k, &vs));
+                ks32 = k;
+            } else {
+                HX_TRY(c->key2.alloc(sizeof(long long) * nkeys));
+                long long *k = nullptr;
+                HX_TRY(rsort::radix_sort_pairs<long long>(c->key.as<long long>(), c->ord.as<unsigned>(), c->key2.as<long long>(),
+                                                          c->v1.as<unsigned>(), nkeys, end_bit, c->sort_tmp, st, &k, &vs));
+                ks64 = k;
+            }
+        }
+        {
+            ProfScope ps("catmap_add");
+            const unsigned blocks = (unsigned)((nkeys + 255) / 256);
+            // one launch per value row for every selection (the row's map rows are those of all selections)
+            for (int f = 0; f < c->nfield; ++f) {
+                if (c->grp[f] != g) continue;
+                for (int r = 0; r < c->nrow[f]; ++r) {
+                    const double *vrow = c->val[f].as<double>() + r * c->cap;
+                    double *const *mrows = c->mrows[f].as<double *>() + r * c->nsel;
+                    if (ks32)
+                        hipLaunchKernelGGL(k_sel_run_add<unsigned>, dim3(blocks), dim3(256), 0, st, (long long)nkeys, ks32, vs, npix1, c->nsel,
+                                           vrow, mrows);
+                    else
+                        hipLaunchKernelGGL(k_sel_run_add<long long>, dim3(blocks), dim3(256), 0, st, (long long)nkeys, ks64, vs, npix1,
+                                           c->nsel, vrow, mrows);
+                }
+            }
+            HX_HIP(hipGetLastError());
+        }
+    }
+    HX_HIP(hipEventRecord(c->ev_done[s], st));
+    if (any_dev) HX_HIP(hipStreamSynchronize(st));
+    else if (any_pinned) HX_HIP(hipStreamSynchronize(cs));
+    return HX_OK;
+}
+
+extern "C" int hx_catmap_moments_sel(hx_catmap_sel *c, double *out, int64_t *bad, int64_t *fcount)
+{
+    HX_TRY(ensure_ready());
+    if (!c || !out || !bad || !fcount) return fail(HX_ERR_ARG, "hx_catmap_moments_sel: bad arguments");
+    hipStream_t st = rt().stream;
+    const int nf = c->nfield, width = c->nsel * nf * 4;
+    std::vector<double> acc(width);
+    std::vector<unsigned long long> cnt(c->n_nan() + c->n_bad() + c->n_fcount() + 1);
+    HX_HIP(hipMemcpyAsync(acc.data(), c->acc.p, sizeof(double) * width, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(cnt.data(), c->counters.p, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    const unsigned long long *nan = cnt.data(), *nbad = nan + c->n_nan(), *fc = nbad + c->n_bad();
+    for (int s = 0; s < c->nsel; ++s) {
+        for (int f = 0; f < nf; ++f) {
+            const int sf = s * nf + f;
+            for (int k = 0; k < 4; ++k) out[4 * sf + k] = acc[4 * sf + k];
+            for (int k = 0; k < 5; ++k) bad[6 * sf + k] = (int64_t)nan[5 * sf + k];
+            bad[6 * sf + 5] = (int64_t)nbad[s * c->ngroup + c->grp[f]];
+        }
+        for (int k = 0; k <= c->nfilt; ++k) fcount[(c->nfilt + 1) * s + k] = (int64_t)fc[(c->nfilt + 1) * s + k];
+    }
+    return HX_OK;
+}
+
+extern "C" int hx_catmap_finish_sel(hx_catmap_sel *c, int sel, int field, double norm, const double *vis)
+{
+    HX_TRY(ensure_ready());
+    if (!c || sel < 0 || sel >= c->nsel || field < 0 || field >= c->nfield) return fail(HX_ERR_ARG, "hx_catmap_finish_sel: bad arguments");
+    const long long npix = 12ll * c->nside[field] * c->nside[field];
+    InView vv;
+    HX_TRY(vv.bind(vis, sizeof(double) * npix));
+    {
+        ProfScope ps("catmap_finish");
+        const long long total = npix * c->nrow[field];
+        const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 65536);
+        hipLaunchKernelGGL(k_cat_finish, dim3(blocks), dim3(256), 0, rt().stream, npix, c->nrow[field], c->map[sel * c->nfield + field], norm,
+                           vv.as<double>());
+        HX_HIP(hipGetLastError());
+    }
+    HX_HIP(hipStreamSynchronize(rt().stream));
+    return HX_OK;
+}

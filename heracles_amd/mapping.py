@@ -13,6 +13,7 @@ maps in a single ``transform_many`` call (``hx_map2alm_list``: one upload pipeli
 reference can observe is kept: the keys of ``out`` in the order of ``data``, a map without ``spin`` metadata taking its field's, and
 the two ``ValueError`` messages (unknown field name, spin mismatch), which are the reference's."""
 
+import ast
 import ctypes as C
 import math
 import warnings
@@ -153,17 +154,20 @@ def _item(key, field, catalog):
     return item
 
 
-def _chunks(items):
+def _chunks(items, cols0=()):
     """Split the fields of one catalogue into contexts of at most _MAX_FIELDS fields, _MAX_GROUPS (nside, lon, lat) groups and
-    _MAX_COLUMNS columns (each context reads the catalogue once)."""
-    chunk, groups, cols = [], set(), []
+    _MAX_COLUMNS columns (each context reads the catalogue once); ``cols0``: columns every context reads first."""
+    chunk, groups, cols = [], set(), list(cols0)
     for it in items:
         g = (it.mapper.nside, *it.lonlat)
         need = [c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None and c not in cols]
         if chunk and (len(chunk) == _MAX_FIELDS or len(groups | {g}) > _MAX_GROUPS or len(cols) + len(need) > _MAX_COLUMNS):
             yield chunk, cols
-            chunk, groups, cols = [], set(), []
+            chunk, groups, cols = [], set(), list(cols0)
             need = [c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None and c not in cols]
+        if len(cols) + len(need) > _MAX_COLUMNS:
+            raise ValueError(f"map_catalogs: field {it.key[0]!r} needs {len(cols) + len(need)} columns in one context (at most "
+                             f"{_MAX_COLUMNS})")
         chunk.append(it)
         groups.add(g)
         cols.extend(need)
@@ -368,6 +372,334 @@ def _map_catalog(items, catalog, device, device_out):
     return results
 
 
+# ---- views of one base catalogue in one pass (hx_catmap_*_sel) -------------------------------------------------------------------------
+
+_MAX_SELECTIONS, _MAX_PREDICATES, _MAX_FILTERS = 32, 64, 4  # HX_CAT_MAX_* of include/hxsht.h
+_OPS = {ast.Eq: 0, ast.NotEq: 1, ast.Lt: 2, ast.LtE: 3, ast.Gt: 4, ast.GtE: 5}  # HX_CAT_EQ .. HX_CAT_GE
+_FILTER_INVALID, _FILTER_FOOTPRINT = 0, 1
+
+
+def _constant(node):
+    """The number of a constant node (``3``, ``-0.5``), else None."""
+    sign = 1
+    if isinstance(node, ast.UnaryOp) and isinstance(node.op, (ast.USub, ast.UAdd)):
+        sign = -1 if isinstance(node.op, ast.USub) else 1
+        node = node.operand
+    if isinstance(node, ast.Constant) and type(node.value) in (int, float):
+        return sign * node.value
+    return None
+
+
+def _compile_predicate(expr, dtypes):
+    """``[(column, op, value), ...]`` for a row filter made of comparisons ``column OP constant`` joined by ``&``, or None when the
+    string is anything else (it is then evaluated per page by the row-filter rule).  Parsed with ``ast``, never evaluated.  ``dtypes``
+    maps the base's column names to their dtypes: a comparison compiles only where float64 gives numpy's answer (float64 columns;
+    integer columns against a constant of magnitude at most 2^53)."""
+    try:
+        tree = ast.parse(expr, mode="eval")
+    except SyntaxError:
+        return None
+    terms = []
+
+    def walk(node):
+        if isinstance(node, ast.BinOp) and isinstance(node.op, ast.BitAnd):
+            return walk(node.left) and walk(node.right)
+        if not (isinstance(node, ast.Compare) and len(node.ops) == 1 and type(node.ops[0]) in _OPS and isinstance(node.left, ast.Name)):
+            return False
+        name, value = node.left.id, _constant(node.comparators[0])
+        dt = dtypes.get(name)
+        if value is None or dt is None:
+            return False
+        dt = np.dtype(dt)
+        if dt == np.float64 or (dt.kind in "iu" and (not float(value).is_integer() or abs(value) <= 2**53)):
+            terms.append((name, _OPS[type(node.ops[0])], float(value)))
+            return True
+        return False
+
+    return terms if walk(tree.body) and terms else None
+
+
+def _dtypes(base):
+    import torch
+
+    return {name: (np.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype) for name, v in base._cols.items()}
+
+
+def _sel_base(catalog):
+    """The base ``ArrayCatalog`` whose one-pass group ``catalog`` joins, or None for the per-catalogue path: a ``heracles_amd`` view, or
+    its base itself, whose filters are all of the two known types."""
+    from .catalog import ArrayCatalog, CatalogView, FootprintFilter, InvalidValueFilter
+
+    base = catalog.base if isinstance(catalog, CatalogView) else catalog
+    if not isinstance(base, ArrayCatalog) or not isinstance(catalog, (ArrayCatalog, CatalogView)):
+        return None
+    if len(base.filters) > _MAX_FILTERS or any(type(f) not in (InvalidValueFilter, FootprintFilter) for f in base.filters):
+        return None
+    if any(isinstance(f, InvalidValueFilter) and not f.columns for f in base.filters):
+        return None  # (a filter that checks no column: the per-catalogue path applies it as it is)
+    return base
+
+
+def _filter_columns(base):
+    """The columns the base's filters read, in order."""
+    from .catalog import FootprintFilter
+
+    cols = []
+    for flt in base.filters:
+        names = flt.lonlat if isinstance(flt, FootprintFilter) else (*flt.columns, *(() if flt.weight is None else (flt.weight,)))
+        cols.extend(c for c in names if c not in cols)
+    return cols
+
+
+def _item_columns(it):
+    return {c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None}
+
+
+def _room(cols0, mapped):
+    """Whether every field of ``mapped`` fits one context next to the columns ``cols0`` (each context reads cols0 first)."""
+    return all(len(set(cols0) | _item_columns(it)) <= _MAX_COLUMNS for it in mapped)
+
+
+def _map_budget(device):
+    """Bytes the maps of one pass may take (a hook tests lower to force a split)."""
+    import torch
+
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(free * 0.8)
+
+
+class _CatMapSel:
+    """One hx_catmap_sel context: the fields of one pass for S selections of one base, and the maps [S][nfields]."""
+
+    def __init__(self, page_size, ncols, desc, nsel, preds, pval, filters, footprints, maps):
+        from . import _lib
+
+        _lib.ensure_init()
+        self._L = _lib.load()
+        self.maps = maps
+        self.nsel, self.nfield, self.nfilt = nsel, len(desc), len(filters)
+        d = np.ascontiguousarray(desc, dtype=np.intc).ravel()
+        p = np.ascontiguousarray(preds, dtype=np.intc).reshape(-1)
+        v = np.ascontiguousarray(pval, dtype=np.float64).reshape(-1)
+        fl = np.ascontiguousarray(filters, dtype=np.intc).reshape(-1)
+        self._keep = (d, p, v, fl, footprints)
+        mp = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+        fp = (C.c_void_p * max(1, len(footprints)))(*[None if f is None else f.data_ptr() for f in footprints])
+        for m in maps:
+            _lib.ptr(m)
+        self._h = self._L.hx_catmap_create_sel(int(page_size), int(ncols), len(desc), d.ctypes.data, int(nsel), len(v),
+                                               p.ctypes.data if len(v) else None, v.ctypes.data if len(v) else None, self.nfilt,
+                                               fl.ctypes.data if self.nfilt else None, fp, mp)
+        if not self._h:
+            raise _lib.HxError(_lib.HX_ERR_ARG, self._L.hx_last_error().decode(errors="replace"))
+        self._lib = _lib
+
+    def page(self, n, cols, mask):
+        ptrs = (C.c_void_p * len(cols))(*[self._lib.ptr(c).value for c in cols])
+        self._lib.check(self._L.hx_catmap_page_sel(self._h, int(n), ptrs, self._lib.ptr(mask)))
+
+    def moments(self):
+        S, nf = self.nsel, self.nfield
+        mom, bad = np.empty((S, nf, 4)), np.empty((S, nf, 6), dtype=np.int64)
+        fcount = np.empty((S, self.nfilt + 1), dtype=np.int64)
+        self._lib.check(self._L.hx_catmap_moments_sel(self._h, mom.ctypes.data, bad.ctypes.data, fcount.ctypes.data))
+        return mom, bad, fcount
+
+    def finish(self, s, f, norm, vis):
+        self._lib.check(self._L.hx_catmap_finish_sel(self._h, int(s), int(f), float(norm), None if vis is None else self._lib.ptr(vis)))
+
+    def close(self):
+        if self._h:
+            self._L.hx_catmap_destroy_sel(self._h)
+            self._h = None
+
+
+def _pack(masks, n, like):
+    """The membership words of a page: bit s set where every mask term of selection s keeps the row (``masks[s]``: a list of boolean
+    page masks, empty for a selection without any).  None when no selection has a mask term."""
+    if not any(masks):
+        return None
+    if hasattr(like, "data_ptr") and like.is_cuda:
+        import torch
+
+        word = torch.zeros(n, dtype=torch.int32, device=like.device)
+        for s, terms in enumerate(masks):
+            keep = torch.ones(n, dtype=torch.bool, device=like.device)
+            for m in terms:
+                keep &= torch.as_tensor(m, device=like.device)
+            word |= keep.to(torch.int32) << s
+        return word
+    word = np.zeros(n, dtype=np.uint32)
+    for s, terms in enumerate(masks):
+        keep = np.ones(n, dtype=bool)
+        for m in terms:
+            keep &= m.cpu().numpy() if hasattr(m, "data_ptr") else np.asarray(m, dtype=bool)
+        word |= keep.astype(np.uint32) << np.uint32(s)
+    return word
+
+
+def _sel_terms(catalog, dtypes, fcols, mapped):
+    """(predicates [(column, op, value)], mask terms) of a view's selection; the base itself selects every row.  A string compiles to
+    predicates only while the view's predicates stay within _MAX_PREDICATES and their columns leave room for every field next to the
+    filters' columns; otherwise it is a mask term (evaluated per page by the row-filter rule: the same rows)."""
+    from .catalog import _flatten
+
+    preds, masks = [], []
+    for term in (() if catalog.base is None else _flatten(catalog.selection)):
+        compiled = _compile_predicate(term, dtypes) if isinstance(term, str) else None
+        if compiled is not None:
+            trial = preds + compiled
+            cols0 = list(dict.fromkeys([*fcols, *(c for c, _, _ in trial)]))
+            if len(trial) > _MAX_PREDICATES or not _room(cols0, mapped):
+                compiled = None
+        if compiled is None:
+            masks.append(term)
+        else:
+            preds.extend(compiled)
+    return preds, masks
+
+
+def _filter_error(fcount):
+    n = int(fcount[-1])
+    if n:
+        return ValueError(f"map_catalogs: {n} positions have a latitude outside [-90, 90] or a non-finite coordinate in a footprint filter "
+                          "(healpy: THETA is out of range [0,pi])")
+    return None
+
+
+def _map_selections(base, entries, terms, device, device_out):
+    """One pass over the pages of ``base`` for the views ``entries`` -- [(key j, catalogue, items)] with the same mapped fields, and
+    their ``terms`` (_sel_terms) --: {j: ({key: map}, error or None, [warning texts])}."""
+    import torch
+
+    from .catalog import CatalogPage, FootprintFilter, _chunk_mask
+
+    filters = list(base.filters)
+    pcols = [c for preds, _ in terms for c, _, _ in preds]
+    cols0 = list(dict.fromkeys([*_filter_columns(base), *pcols]))
+    done = {j: ({}, None, []) for j, _, _ in entries}
+    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
+    cap = max(1, int(base.page_size))
+    S = len(entries)
+    for chunk, cols in _chunks(mapped, cols0):
+        index = {c: i for i, c in enumerate(cols)}
+        fdesc, footprints = [], []
+        for flt in filters:
+            if isinstance(flt, FootprintFilter):
+                fp = flt.footprint
+                fp = (fp if hasattr(fp, "data_ptr") else torch.as_tensor(np.ascontiguousarray(np.asarray(fp), dtype=np.float64)))
+                fp = fp.to(device=device, dtype=torch.float64).contiguous()
+                fdesc.append([_FILTER_FOOTPRINT, index[flt.lonlat[0]], index[flt.lonlat[1]], flt.nside])
+                footprints.append(fp)
+            else:
+                bits = 0
+                for c in flt.columns:
+                    bits |= 1 << index[c]
+                fdesc.append([_FILTER_INVALID, bits, -1 if flt.weight is None else index[flt.weight], 0])
+                footprints.append(None)
+        preds, pval = [], []
+        for s, (ps, _) in enumerate(terms):
+            for c, op, v in ps:
+                preds.append([s, index[c], op])
+                pval.append(v)
+        desc = []
+        for it in chunk:
+            ix = lambda c: -1 if c is None else index[c]
+            desc.append([it.kind, it.mapper.nside, ix(it.lonlat[0]), ix(it.lonlat[1]), ix(it.value), ix(it.imag), ix(it.weight)])
+        maps = [_new_map(2 if it.kind == _COMPLEX else 1, 12 * it.mapper.nside**2, device) for _ in range(S) for it in chunk]
+        ctx = _CatMapSel(cap, len(cols), desc, S, preds, pval, fdesc, footprints, maps)
+        try:
+            for start in range(0, base.size, cap):
+                stop = min(base.size, start + cap)
+                page = {c: base._cols[c][start:stop] for c in base._cols}
+                view = CatalogPage(page)
+                arrays = [_column(view[c], device) for c in cols]
+                masks = [[_chunk_mask(t, page, start, stop) for t in m] for _, m in terms]
+                ctx.page(stop - start, arrays, _pack(masks, stop - start, arrays[0]))
+                del arrays, page, view, masks
+            mom, bad, fcount = ctx.moments()
+            for s, (j, cat, items) in enumerate(entries):
+                res, err, warns = done[j]
+                if err is None:
+                    err = _filter_error(fcount[s])
+                if err is None:
+                    try:
+                        _check_page_errors(chunk, bad[s])
+                    except ValueError as e:
+                        err = e
+                for k, flt in enumerate(filters):
+                    if not isinstance(flt, FootprintFilter) and flt.warn and fcount[s, k] and "WARNING: catalog contains invalid values" not in warns:
+                        warns.append("WARNING: catalog contains invalid values")
+                done[j] = (res, err, warns)
+                if err is not None:
+                    continue
+                byname = {it.key[0]: it for it in items}
+                for f, it0 in enumerate(chunk):
+                    it = byname[it0.key[0]]
+                    with warnings.catch_warnings(record=True) as rec:
+                        warnings.simplefilter("always")
+                        norm, extra = _normalise(it, mom[s, f], cat)
+                        vis = None
+                        if it.kind == _POSITIONS and it.field.overdensity:
+                            vis = _visibility_on(cat, it.mapper.nside, device, "positions and visibility have different size")
+                    warns.extend(str(w.message) for w in rec if str(w.message) not in warns)
+                    ctx.finish(s, f, norm, vis)
+                    res[it.key] = _result(it, maps[s * len(chunk) + f], cat, extra, device_out)
+        finally:
+            ctx.close()
+    return done
+
+
+def _sel_groups(entries, terms, fcols, device):
+    """Split one base's views [(j, catalogue, items)] and their terms into passes, in order: at most _MAX_SELECTIONS views, the maps
+    within the budget, at most _MAX_PREDICATES predicates, and predicate columns that leave room for every field next to ``fcols``."""
+    if not entries:
+        return []
+    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
+    per_view = sum(8 * (2 if it.kind == _COMPLEX else 1) * 12 * it.mapper.nside**2 for it in mapped)
+    most = max(1, min(_MAX_SELECTIONS, _map_budget(device) // max(1, per_view)))
+    parts, cur, npred, pcols = [], [], 0, []
+    for entry, term in zip(entries, terms):
+        mine = [c for c, _, _ in term[0]]
+        cols0 = list(dict.fromkeys([*fcols, *pcols, *mine]))
+        if cur and (len(cur) == most or npred + len(term[0]) > _MAX_PREDICATES or not _room(cols0, mapped)):
+            parts.append(cur)
+            cur, npred, pcols = [], 0, []
+        cur.append((entry, term))
+        npred += len(term[0])
+        pcols.extend(c for c in mine if c not in pcols)
+    parts.append(cur)
+    return parts
+
+
+def _plan_groups(fields, catalogs, include, exclude):
+    """{j: (base, field names)} for the catalogues that go through one-pass groups; a group is used when it holds a view or the base
+    has filters (a plain catalogue keeps the per-catalogue path)."""
+    from .catalog import CatalogView
+
+    members = {}
+    for j, catalog in catalogs.items():
+        base = _sel_base(catalog)
+        if base is None:
+            continue
+        names = tuple(i for i in fields if toc_match((i, j), include, exclude))
+        if names:
+            members.setdefault((id(base), names), []).append(j)
+    plan = {}
+    for (bid, names), js in members.items():
+        base = _sel_base(catalogs[js[0]])
+        fcols = set(_filter_columns(base))
+        for i in names:  # every field must fit one context next to the filters' columns, else the per-catalogue path
+            cols = getattr(fields[i], "columns", None) or ()
+            if len(fcols | set(cols[:2]) | {c for c in cols[2:] if c is not None}) > _MAX_COLUMNS:
+                break
+        else:
+            if base.filters or any(isinstance(catalogs[j], CatalogView) for j in js):
+                for j in js:
+                    plan[j] = (base, names)
+    return plan
+
+
 def map_catalogs(fields, catalogs, *, parallel=False, out=None, include=None, exclude=None, progress=None, device=None):
     """Maps of ``fields`` for every catalogue of ``catalogs``: ``out[field name, catalogue key]`` (any mutable mapping; a ``TocDict``
     by default), in the reference's order, filtered by ``include`` / ``exclude`` (``toc_match``).  ``progress.update(current, total)``
@@ -384,7 +716,26 @@ def map_catalogs(fields, catalogs, *, parallel=False, out=None, include=None, ex
     if progress is not None:
         progress.update(current, total)
     dev = None
+    plan = _plan_groups(fields, catalogs, include, exclude)
+    staged = {}  # j -> ({key: map}, error, warning texts) of the one-pass groups, emitted in the order of the catalogues
     for j, catalog in catalogs.items():
+        if j in plan and j not in staged:
+            if dev is None:
+                dev = _device_of(device)
+            _run_group(fields, catalogs, plan, j, include, exclude, dev, device is not None, staged)
+        if j in staged:
+            results, err, warns = staged.pop(j)
+            for text in warns:
+                warnings.warn(text)
+            if err is not None:
+                raise err
+            for key in results:
+                out[key] = results[key]
+                current += 1
+                if progress is not None:
+                    progress.update(current, total)
+            del results
+            continue
         items = [_item((i, j), field, catalog) for i, field in fields.items() if toc_match((i, j), include, exclude)]
         if not items:
             continue
@@ -398,3 +749,44 @@ def map_catalogs(fields, catalogs, *, parallel=False, out=None, include=None, ex
                 progress.update(current, total)
         del results
     return out
+
+
+def _run_group(fields, catalogs, plan, first, include, exclude, device, device_out, staged):
+    """Maps every catalogue of the group of ``first`` in one pass per split, into ``staged``; the item checks of each catalogue run
+    first, and a catalogue that fails them keeps its error (raised in its turn)."""
+    base, names = plan[first]
+    entries = []
+    for j, catalog in catalogs.items():
+        if plan.get(j) is None or plan[j][0] is not base or plan[j][1] != names:
+            continue
+        try:
+            items = [_item((i, j), fields[i], catalog) for i in names]
+        except (ValueError, TypeError, NotImplementedError) as e:
+            staged[j] = ({}, e, [])
+            continue
+        vis_res, warns = {}, []
+        for it in items:
+            if it.kind == _VISIBILITY:
+                with warnings.catch_warnings(record=True) as rec:
+                    warnings.simplefilter("always")
+                    vis = _visibility_on(catalog, it.mapper.nside, device, "changing size of visibility map")
+                warns.extend(str(w.message) for w in rec if str(w.message) not in warns)
+                if catalog.visibility is vis:
+                    vis = vis.clone()
+                vis_res[it.key] = _result(it, vis, catalog, {}, device_out)
+        staged[j] = (vis_res, None, warns)
+        entries.append((j, catalog, items))
+    if not entries or all(it.kind == _VISIBILITY for it in entries[0][2]):
+        for j, _, items in entries:
+            staged[j] = ({it.key: staged[j][0][it.key] for it in items}, None, staged[j][2])
+        return
+    dtypes, fcols = _dtypes(base), _filter_columns(base)
+    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
+    terms = [_sel_terms(cat, dtypes, fcols, mapped) for _, cat, _ in entries]
+    for part in _sel_groups(entries, terms, fcols, device):
+        done = _map_selections(base, [e for e, _ in part], [t for _, t in part], device, device_out)
+        for (j, catalog, items), _ in part:
+            res, err, warns = done[j]
+            vis_res, _, w0 = staged[j]
+            allres = {**vis_res, **res}
+            staged[j] = ({it.key: allres[it.key] for it in items} if err is None else {}, err, [*w0, *[w for w in warns if w not in w0]])

@@ -331,6 +331,45 @@ int hx_catmap_moments(hx_catmap *ctx, double *out, int64_t *bad);
 int hx_catmap_finish(hx_catmap *ctx, int field, double norm, const double *vis);
 void hx_catmap_destroy(hx_catmap *ctx);
 
+/* ---- selections: the views of ONE base catalogue (base.where(selection)) mapped in one pass over the base's pages ------------------
+ * hx_catmap_create_sel: nsel <= HX_CAT_MAX_SELECTIONS selections, the fields desc of hx_catmap_create (the same fields for every
+ * selection), maps[s nfields + f] the DEVICE map of field f for selection s.  Bit s of a row's membership word is set when the base's
+ * filters keep the row, its mask word has bit s (hx_catmap_page_sel) and every predicate term of selection s holds:
+ *  preds:   npred <= HX_CAT_MAX_PREDICATES terms of 3 ints {selection, column, op} (op one of HX_CAT_EQ .. HX_CAT_GE), pval[npred] their
+ *           constants: `column op pval` compared in float64 as numpy does (NaN: false, except HX_CAT_NE: true).
+ *  filters: nfilt <= HX_CAT_MAX_FILTERS descriptors of 4 ints {type, a, b, nside}, applied in order to the rows of any selection:
+ *           HX_CAT_FILTER_INVALID   a = bitmask of the columns checked, b = the weight column or -1: the row goes when one of the columns
+ *                                   is NaN and (b < 0 or its weight != 0)  (heracles/catalog/filters.py:47-59);
+ *           HX_CAT_FILTER_FOOTPRINT a, b = lon, lat columns; footprints[k]: the filter's DEVICE map [12 nside^2] (RING): the row goes when
+ *                                   footprint[ang2pix(nside, lon, lat)] == 0; an invalid position is counted and the row goes.
+ *  hx_catmap_page_sel:    hx_catmap_page plus mask[n] (host, device, or NULL: every bit set).  One stable sort per (nside, lon, lat)
+ *                         group by the key (selection, pixel) serves every selection; a row in k > 1 selections enters it k times, in
+ *                         catalogue order.  Per pixel every selection's rows add in catalogue order: a selection's map equals the map
+ *                         of a catalogue holding exactly its rows, bit for bit.
+ *  hx_catmap_moments_sel: out[4 (s nfields + f) + k] and bad[6 (s nfields + f) + k] as hx_catmap_moments, over the rows of selection s;
+ *                         fcount[(nfilt + 1) s + k]: rows of s removed by filter k (k < nfilt; after the filters before it), and at
+ *                         k = nfilt the rows of s with an invalid position in a footprint filter.  The moments are summed per wave and
+ *                         block in a fixed order, then over blocks: bitwise repeatable (not the summation order of hx_catmap).
+ *  hx_catmap_finish_sel:  hx_catmap_finish for the map of (sel, field).                                                            */
+typedef struct hx_catmap_sel hx_catmap_sel;
+#define HX_CAT_MAX_SELECTIONS 32
+#define HX_CAT_MAX_PREDICATES 64
+#define HX_CAT_MAX_FILTERS 4
+#define HX_CAT_EQ 0
+#define HX_CAT_NE 1
+#define HX_CAT_LT 2
+#define HX_CAT_LE 3
+#define HX_CAT_GT 4
+#define HX_CAT_GE 5
+#define HX_CAT_FILTER_INVALID 0
+#define HX_CAT_FILTER_FOOTPRINT 1
+hx_catmap_sel *hx_catmap_create_sel(int64_t page_size, int ncols, int nfields, const int *desc, int nsel, int npred, const int *preds,
+                                    const double *pval, int nfilt, const int *filters, const double *const *footprints, double *const *maps);
+int hx_catmap_page_sel(hx_catmap_sel *ctx, int64_t n, const double *const *cols, const uint32_t *mask);
+int hx_catmap_moments_sel(hx_catmap_sel *ctx, double *out, int64_t *bad, int64_t *fcount);
+int hx_catmap_finish_sel(hx_catmap_sel *ctx, int sel, int field, double norm, const double *vis);
+void hx_catmap_destroy_sel(hx_catmap_sel *ctx);
+
 /* healpy's pixel-weight files (`healpix_full_weights_nside_NNNN.fits`, the data hp.map2alm(use_pixel_weights=True, datapath=...)
  * of heracles/healpy.py:183-189 reads): expansion of the compressed half-quadrant weights -- hx_pixel_weights_size(nside) =
  * (nside + 1)(3 nside + 1) / 4 values -- to the full-sky array [12 nside^2] of multiplicative pixel weights 1 + w that hx_map2alm
