@@ -17,6 +17,7 @@ import ast
 import ctypes as C
 import math
 import warnings
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Any
 
@@ -107,6 +108,21 @@ class _Item:
     imag: Any = None
     weight: Any = None
 
+    @property
+    def columns(self):
+        """The columns the field reads, in the order of the reference's ``columns``."""
+        return _read((*self.lonlat, self.value, self.imag, self.weight))
+
+
+def _read(columns):
+    """The columns of a field's ``columns`` tuple that name one (an optional column is None)."""
+    return tuple(c for c in columns if c is not None)
+
+
+def _mapped(items):
+    """The items that need a pass over the catalogue."""
+    return [it for it in items if it.kind != _VISIBILITY]
+
 
 def _kind(field):
     for cls in type(field).__mro__:
@@ -160,17 +176,16 @@ def _chunks(items, cols0=()):
     chunk, groups, cols = [], set(), list(cols0)
     for it in items:
         g = (it.mapper.nside, *it.lonlat)
-        need = [c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None and c not in cols]
-        if chunk and (len(chunk) == _MAX_FIELDS or len(groups | {g}) > _MAX_GROUPS or len(cols) + len(need) > _MAX_COLUMNS):
+        need = lambda: [c for c in it.columns if c not in cols]
+        if chunk and (len(chunk) == _MAX_FIELDS or len(groups | {g}) > _MAX_GROUPS or len(cols) + len(need()) > _MAX_COLUMNS):
             yield chunk, cols
             chunk, groups, cols = [], set(), list(cols0)
-            need = [c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None and c not in cols]
-        if len(cols) + len(need) > _MAX_COLUMNS:
-            raise ValueError(f"map_catalogs: field {it.key[0]!r} needs {len(cols) + len(need)} columns in one context (at most "
+        if len(cols) + len(need()) > _MAX_COLUMNS:
+            raise ValueError(f"map_catalogs: field {it.key[0]!r} needs {len(cols) + len(need())} columns in one context (at most "
                              f"{_MAX_COLUMNS})")
         chunk.append(it)
         groups.add(g)
-        cols.extend(need)
+        cols.extend(need())
     if chunk:
         yield chunk, cols
 
@@ -194,28 +209,46 @@ def _column(x, device):
     return np.ascontiguousarray(_native(np.asarray(x)), dtype=np.float64)
 
 
-class _CatMap:
-    """One hx_catmap context: the fields of one catalogue (at most _MAX_FIELDS) and their device maps."""
+class _Context:
+    """What the two contexts share: the library, the device maps (handed over from torch's stream, which zero-filled them) and the
+    handle."""
 
-    def __init__(self, page_size, ncols, desc, maps):
+    _destroy = None  # name of the entry point that frees the handle
+
+    def _open(self, maps):
         from . import _lib
 
         _lib.ensure_init()
-        self._L = _lib.load()
+        self._lib, self._L, self._h = _lib, _lib.load(), None
         self.maps = maps
-        d = np.ascontiguousarray(desc, dtype=np.intc).ravel()
-        self._desc = d
-        ptrs = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
-        for m in maps:  # (torch zero-filled them on its own stream)
-            _lib.ptr(m)
-        self._h = self._L.hx_catmap_create(int(page_size), int(ncols), len(maps), d.ctypes.data, ptrs)
-        if not self._h:
-            raise _lib.HxError(_lib.HX_ERR_ARG, self._L.hx_last_error().decode(errors="replace"))
-        self._lib = _lib
+        return (C.c_void_p * len(maps))(*[_lib.ptr(m).value for m in maps])
+
+    def _created(self, handle):
+        if not handle:
+            raise self._lib.HxError(self._lib.HX_ERR_ARG, self._L.hx_last_error().decode(errors="replace"))
+        self._h = handle
+
+    def _pointers(self, cols):
+        return (C.c_void_p * len(cols))(*[self._lib.ptr(c).value for c in cols])
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+
+class _CatMap(_Context):
+    """One hx_catmap context: the fields of one catalogue (at most _MAX_FIELDS) and their device maps."""
+
+    _destroy = "hx_catmap_destroy"
+
+    def __init__(self, page_size, ncols, desc, maps):
+        ptrs = self._open(maps)
+        d = self._desc = np.ascontiguousarray(desc, dtype=np.intc).ravel()
+        self._created(self._L.hx_catmap_create(int(page_size), int(ncols), len(maps), d.ctypes.data, ptrs))
 
     def page(self, n, cols):
-        ptrs = (C.c_void_p * len(cols))(*[self._lib.ptr(c).value for c in cols])
-        self._lib.check(self._L.hx_catmap_page(self._h, int(n), ptrs))
+        self._lib.check(self._L.hx_catmap_page(self._h, int(n), self._pointers(cols)))
 
     def moments(self):
         nf = len(self.maps)
@@ -224,12 +257,7 @@ class _CatMap:
         return mom, bad
 
     def finish(self, f, norm, vis):
-        self._lib.check(self._L.hx_catmap_finish(self._h, int(f), float(norm), None if vis is None else self._lib.ptr(vis)))
-
-    def close(self):
-        if self._h:
-            self._L.hx_catmap_destroy(self._h)
-            self._h = None
+        self._lib.check(self._L.hx_catmap_finish(self._h, int(f), float(norm), self._lib.ptr(vis)))
 
 
 def _device_of(device):
@@ -331,25 +359,66 @@ def _iter_pages(catalog, cap):
             yield page, start, min(n, start + cap)
 
 
-def _map_catalog(items, catalog, device, device_out):
-    """Maps of the ``items`` (already checked, in field order) of one catalogue; {key: map}."""
+def _add_texts(texts, new):
+    """Appends the texts of ``new`` not yet in ``texts``, in order."""
+    for text in new:
+        if text not in texts:
+            texts.append(text)
+
+
+@contextmanager
+def _collect(texts):
+    """Records the warnings raised inside instead of showing them: their texts go to ``texts``, each once (map_catalogs raises them in
+    the catalogue's turn).  ``texts`` None: the warnings are shown as they come."""
+    if texts is None:
+        yield
+        return
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        yield
+    _add_texts(texts, (str(w.message) for w in rec))
+
+
+def _map_visibility(items, catalog, device, device_out, texts=None):
+    """{key: map} of the ``Visibility`` items of a catalogue: its visibility at the field's resolution.  ``texts``: where the
+    resampling warnings go (_collect)."""
     results = {}
     for it in items:
-        if it.kind == _VISIBILITY:
-            nside = it.mapper.nside
-            vis = _visibility_on(catalog, nside, device, "changing size of visibility map")
-            if catalog.visibility is vis:  # (a device visibility of the right size: the map is a copy, as the reference's out[:] = vis)
-                vis = vis.clone()
-            results[it.key] = _result(it, vis, catalog, {}, device_out)
-    mapped = [it for it in items if it.kind != _VISIBILITY]
+        if it.kind != _VISIBILITY:
+            continue
+        with _collect(texts):
+            vis = _visibility_on(catalog, it.mapper.nside, device, "changing size of visibility map")
+        if catalog.visibility is vis:  # (a device visibility of the right size: the map is a copy, as the reference's out[:] = vis)
+            vis = vis.clone()
+        results[it.key] = _result(it, vis, catalog, {}, device_out)
+    return results
+
+
+def _context_inputs(chunk, cols, nsel, device):
+    """The descriptors of hx_catmap_create (7 ints per field: kind, nside and the indices in ``cols`` of lon, lat, value, imaginary
+    part and weight, -1 for none) and the zeroed device maps [nsel][fields] of one context."""
+    index = {c: i for i, c in enumerate(cols)}
+    ix = lambda c: -1 if c is None else index[c]
+    desc = [[it.kind, it.mapper.nside, ix(it.lonlat[0]), ix(it.lonlat[1]), ix(it.value), ix(it.imag), ix(it.weight)] for it in chunk]
+    maps = [_new_map(2 if it.kind == _COMPLEX else 1, 12 * it.mapper.nside**2, device) for _ in range(nsel) for it in chunk]
+    return desc, maps
+
+
+def _norm_and_visibility(it, mom, catalog, device):
+    """What ``finish`` needs for one field of one catalogue: (norm, visibility map or None), and the metadata of _normalise."""
+    norm, extra = _normalise(it, mom, catalog)
+    vis = None
+    if it.kind == _POSITIONS and it.field.overdensity:
+        vis = _visibility_on(catalog, it.mapper.nside, device, "positions and visibility have different size")
+    return (norm, vis), extra
+
+
+def _map_catalog(items, catalog, device, device_out):
+    """Maps of the ``items`` (already checked) of one catalogue; {key: map} in the order of the items."""
+    results = _map_visibility(items, catalog, device, device_out)
     cap = max(1, int(catalog.page_size))
-    for chunk, cols in _chunks(mapped):
-        index = {c: i for i, c in enumerate(cols)}
-        desc, maps = [], []
-        for it in chunk:
-            ix = lambda c: -1 if c is None else index[c]
-            desc.append([it.kind, it.mapper.nside, ix(it.lonlat[0]), ix(it.lonlat[1]), ix(it.value), ix(it.imag), ix(it.weight)])
-            maps.append(_new_map(2 if it.kind == _COMPLEX else 1, 12 * it.mapper.nside**2, device))
+    for chunk, cols in _chunks(_mapped(items)):
+        desc, maps = _context_inputs(chunk, cols, 1, device)
         ctx = _CatMap(cap, len(cols), desc, maps)
         try:
             for page, start, stop in _iter_pages(catalog, cap):
@@ -361,15 +430,12 @@ def _map_catalog(items, catalog, device, device_out):
             mom, bad = ctx.moments()
             _check_page_errors(chunk, bad)
             for f, it in enumerate(chunk):
-                norm, extra = _normalise(it, mom[f], catalog)
-                vis = None
-                if it.kind == _POSITIONS and it.field.overdensity:
-                    vis = _visibility_on(catalog, it.mapper.nside, device, "positions and visibility have different size")
-                ctx.finish(f, norm, vis)
-                results[it.key] = _result(it, ctx.maps[f], catalog, extra, device_out)
+                finish, extra = _norm_and_visibility(it, mom[f], catalog, device)
+                ctx.finish(f, *finish)
+                results[it.key] = _result(it, maps[f], catalog, extra, device_out)
         finally:
             ctx.close()
-    return results
+    return {it.key: results[it.key] for it in items}
 
 
 # ---- views of one base catalogue in one pass (hx_catmap_*_sel) -------------------------------------------------------------------------
@@ -451,13 +517,9 @@ def _filter_columns(base):
     return cols
 
 
-def _item_columns(it):
-    return {c for c in (*it.lonlat, it.value, it.imag, it.weight) if c is not None}
-
-
 def _room(cols0, mapped):
     """Whether every field of ``mapped`` fits one context next to the columns ``cols0`` (each context reads cols0 first)."""
-    return all(len(set(cols0) | _item_columns(it)) <= _MAX_COLUMNS for it in mapped)
+    return all(len({*cols0, *it.columns}) <= _MAX_COLUMNS for it in mapped)
 
 
 def _map_budget(device):
@@ -468,35 +530,26 @@ def _map_budget(device):
     return int(free * 0.8)
 
 
-class _CatMapSel:
+class _CatMapSel(_Context):
     """One hx_catmap_sel context: the fields of one pass for S selections of one base, and the maps [S][nfields]."""
 
-    def __init__(self, page_size, ncols, desc, nsel, preds, pval, filters, footprints, maps):
-        from . import _lib
+    _destroy = "hx_catmap_destroy_sel"
 
-        _lib.ensure_init()
-        self._L = _lib.load()
-        self.maps = maps
+    def __init__(self, page_size, ncols, desc, nsel, preds, pval, filters, footprints, maps):
+        mp = self._open(maps)
         self.nsel, self.nfield, self.nfilt = nsel, len(desc), len(filters)
         d = np.ascontiguousarray(desc, dtype=np.intc).ravel()
         p = np.ascontiguousarray(preds, dtype=np.intc).reshape(-1)
         v = np.ascontiguousarray(pval, dtype=np.float64).reshape(-1)
         fl = np.ascontiguousarray(filters, dtype=np.intc).reshape(-1)
         self._keep = (d, p, v, fl, footprints)
-        mp = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
         fp = (C.c_void_p * max(1, len(footprints)))(*[None if f is None else f.data_ptr() for f in footprints])
-        for m in maps:
-            _lib.ptr(m)
-        self._h = self._L.hx_catmap_create_sel(int(page_size), int(ncols), len(desc), d.ctypes.data, int(nsel), len(v),
-                                               p.ctypes.data if len(v) else None, v.ctypes.data if len(v) else None, self.nfilt,
-                                               fl.ctypes.data if self.nfilt else None, fp, mp)
-        if not self._h:
-            raise _lib.HxError(_lib.HX_ERR_ARG, self._L.hx_last_error().decode(errors="replace"))
-        self._lib = _lib
+        self._created(self._L.hx_catmap_create_sel(int(page_size), int(ncols), len(desc), d.ctypes.data, int(nsel), len(v),
+                                                   p.ctypes.data if len(v) else None, v.ctypes.data if len(v) else None, self.nfilt,
+                                                   fl.ctypes.data if self.nfilt else None, fp, mp))
 
     def page(self, n, cols, mask):
-        ptrs = (C.c_void_p * len(cols))(*[self._lib.ptr(c).value for c in cols])
-        self._lib.check(self._L.hx_catmap_page_sel(self._h, int(n), ptrs, self._lib.ptr(mask)))
+        self._lib.check(self._L.hx_catmap_page_sel(self._h, int(n), self._pointers(cols), self._lib.ptr(mask)))
 
     def moments(self):
         S, nf = self.nsel, self.nfield
@@ -506,12 +559,7 @@ class _CatMapSel:
         return mom, bad, fcount
 
     def finish(self, s, f, norm, vis):
-        self._lib.check(self._L.hx_catmap_finish_sel(self._h, int(s), int(f), float(norm), None if vis is None else self._lib.ptr(vis)))
-
-    def close(self):
-        if self._h:
-            self._L.hx_catmap_destroy_sel(self._h)
-            self._h = None
+        self._lib.check(self._L.hx_catmap_finish_sel(self._h, int(s), int(f), float(norm), self._lib.ptr(vis)))
 
 
 def _pack(masks, n, like):
@@ -578,10 +626,9 @@ def _map_selections(base, entries, terms, device, device_out):
     pcols = [c for preds, _ in terms for c, _, _ in preds]
     cols0 = list(dict.fromkeys([*_filter_columns(base), *pcols]))
     done = {j: ({}, None, []) for j, _, _ in entries}
-    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
     cap = max(1, int(base.page_size))
     S = len(entries)
-    for chunk, cols in _chunks(mapped, cols0):
+    for chunk, cols in _chunks(_mapped(entries[0][2]), cols0):
         index = {c: i for i, c in enumerate(cols)}
         fdesc, footprints = [], []
         for flt in filters:
@@ -602,11 +649,7 @@ def _map_selections(base, entries, terms, device, device_out):
             for c, op, v in ps:
                 preds.append([s, index[c], op])
                 pval.append(v)
-        desc = []
-        for it in chunk:
-            ix = lambda c: -1 if c is None else index[c]
-            desc.append([it.kind, it.mapper.nside, ix(it.lonlat[0]), ix(it.lonlat[1]), ix(it.value), ix(it.imag), ix(it.weight)])
-        maps = [_new_map(2 if it.kind == _COMPLEX else 1, 12 * it.mapper.nside**2, device) for _ in range(S) for it in chunk]
+        desc, maps = _context_inputs(chunk, cols, S, device)
         ctx = _CatMapSel(cap, len(cols), desc, S, preds, pval, fdesc, footprints, maps)
         try:
             for start in range(0, base.size, cap):
@@ -628,22 +671,17 @@ def _map_selections(base, entries, terms, device, device_out):
                     except ValueError as e:
                         err = e
                 for k, flt in enumerate(filters):
-                    if not isinstance(flt, FootprintFilter) and flt.warn and fcount[s, k] and "WARNING: catalog contains invalid values" not in warns:
-                        warns.append("WARNING: catalog contains invalid values")
+                    if not isinstance(flt, FootprintFilter) and flt.warn and fcount[s, k]:
+                        _add_texts(warns, ["WARNING: catalog contains invalid values"])
                 done[j] = (res, err, warns)
                 if err is not None:
                     continue
                 byname = {it.key[0]: it for it in items}
                 for f, it0 in enumerate(chunk):
                     it = byname[it0.key[0]]
-                    with warnings.catch_warnings(record=True) as rec:
-                        warnings.simplefilter("always")
-                        norm, extra = _normalise(it, mom[s, f], cat)
-                        vis = None
-                        if it.kind == _POSITIONS and it.field.overdensity:
-                            vis = _visibility_on(cat, it.mapper.nside, device, "positions and visibility have different size")
-                    warns.extend(str(w.message) for w in rec if str(w.message) not in warns)
-                    ctx.finish(s, f, norm, vis)
+                    with _collect(warns):
+                        finish, extra = _norm_and_visibility(it, mom[s, f], cat, device)
+                    ctx.finish(s, f, *finish)
                     res[it.key] = _result(it, maps[s * len(chunk) + f], cat, extra, device_out)
         finally:
             ctx.close()
@@ -655,7 +693,7 @@ def _sel_groups(entries, terms, fcols, device):
     within the budget, at most _MAX_PREDICATES predicates, and predicate columns that leave room for every field next to ``fcols``."""
     if not entries:
         return []
-    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
+    mapped = _mapped(entries[0][2])
     per_view = sum(8 * (2 if it.kind == _COMPLEX else 1) * 12 * it.mapper.nside**2 for it in mapped)
     most = max(1, min(_MAX_SELECTIONS, _map_budget(device) // max(1, per_view)))
     parts, cur, npred, pcols = [], [], 0, []
@@ -690,8 +728,7 @@ def _plan_groups(fields, catalogs, include, exclude):
         base = _sel_base(catalogs[js[0]])
         fcols = set(_filter_columns(base))
         for i in names:  # every field must fit one context next to the filters' columns, else the per-catalogue path
-            cols = getattr(fields[i], "columns", None) or ()
-            if len(fcols | set(cols[:2]) | {c for c in cols[2:] if c is not None}) > _MAX_COLUMNS:
+            if len(fcols | set(_read(getattr(fields[i], "columns", None) or ()))) > _MAX_COLUMNS:
                 break
         else:
             if base.filters or any(isinstance(catalogs[j], CatalogView) for j in js):
@@ -729,25 +766,18 @@ def map_catalogs(fields, catalogs, *, parallel=False, out=None, include=None, ex
                 warnings.warn(text)
             if err is not None:
                 raise err
-            for key in results:
-                out[key] = results[key]
-                current += 1
-                if progress is not None:
-                    progress.update(current, total)
-            del results
-            continue
-        items = [_item((i, j), field, catalog) for i, field in fields.items() if toc_match((i, j), include, exclude)]
-        if not items:
-            continue
-        if dev is None:
-            dev = _device_of(device)
-        results = _map_catalog(items, catalog, dev, device is not None)
-        for it in items:
-            out[it.key] = results[it.key]
+        else:
+            items = [_item((i, j), field, catalog) for i, field in fields.items() if toc_match((i, j), include, exclude)]
+            if not items:
+                continue
+            if dev is None:
+                dev = _device_of(device)
+            results = _map_catalog(items, catalog, dev, device is not None)
+        for key in list(results):
+            out[key] = results.pop(key)
             current += 1
             if progress is not None:
                 progress.update(current, total)
-        del results
     return out
 
 
@@ -764,29 +794,21 @@ def _run_group(fields, catalogs, plan, first, include, exclude, device, device_o
         except (ValueError, TypeError, NotImplementedError) as e:
             staged[j] = ({}, e, [])
             continue
-        vis_res, warns = {}, []
-        for it in items:
-            if it.kind == _VISIBILITY:
-                with warnings.catch_warnings(record=True) as rec:
-                    warnings.simplefilter("always")
-                    vis = _visibility_on(catalog, it.mapper.nside, device, "changing size of visibility map")
-                warns.extend(str(w.message) for w in rec if str(w.message) not in warns)
-                if catalog.visibility is vis:
-                    vis = vis.clone()
-                vis_res[it.key] = _result(it, vis, catalog, {}, device_out)
-        staged[j] = (vis_res, None, warns)
+        warns = []
+        staged[j] = (_map_visibility(items, catalog, device, device_out, warns), None, warns)
         entries.append((j, catalog, items))
-    if not entries or all(it.kind == _VISIBILITY for it in entries[0][2]):
+    mapped = _mapped(entries[0][2]) if entries else []
+    if not mapped:
         for j, _, items in entries:
             staged[j] = ({it.key: staged[j][0][it.key] for it in items}, None, staged[j][2])
         return
     dtypes, fcols = _dtypes(base), _filter_columns(base)
-    mapped = [it for it in entries[0][2] if it.kind != _VISIBILITY]
     terms = [_sel_terms(cat, dtypes, fcols, mapped) for _, cat, _ in entries]
     for part in _sel_groups(entries, terms, fcols, device):
         done = _map_selections(base, [e for e, _ in part], [t for _, t in part], device, device_out)
         for (j, catalog, items), _ in part:
-            res, err, warns = done[j]
-            vis_res, _, w0 = staged[j]
+            res, err, new = done[j]
+            vis_res, _, warns = staged[j]
+            _add_texts(warns, new)
             allres = {**vis_res, **res}
-            staged[j] = ({it.key: allres[it.key] for it in items} if err is None else {}, err, [*w0, *[w for w in warns if w not in w0]])
+            staged[j] = ({it.key: allres[it.key] for it in items} if err is None else {}, err, warns)
