@@ -229,7 +229,8 @@ def synchronize():
 
 def release_caches():
     """Hand back the HBM the library keeps between calls outside plans and contexts: the cache of ``mixmat`` / ``mixmat_eb`` (tables of
-    the last sizes + host-staging buffer, ~3 GB at L = 6144) and the buffers of ``alm2cl_pairs`` (<= 512 MB): hx_release_caches."""
+    the last sizes + host-staging buffer, ~3 GB at L = 6144), the buffers of ``alm2cl_pairs`` (<= 512 MB) and the nodes, weights and
+    Wigner tables ``cl2corr`` / ``corr2cl`` / ``naturalspice`` keep for their last lmax (1.2 GB at lmax 6144): hx_release_caches."""
     check(load().hx_release_caches())
 
 

@@ -1042,12 +1042,15 @@ extern "C" double hx_mixmat_gemm_clock(void)
 
 // Everything the library keeps in HBM between calls outside a plan or a context: the one-shot mixing-matrix cache above (tables of the
 // last (l1max, l2max, l3max), the staging buffer of a host destination -- which hx_mixctx_apply shares --, the staged mask spectrum:
-// ~3 GB at L = 6144) and the buffers of hx_alm2cl_pairs (tables, partial sums, staging: up to 512 MB).  The next call allocates again.
+// ~3 GB at L = 6144), the buffers of hx_alm2cl_pairs (tables, partial sums, staging: up to 512 MB) and the nodes, weights and Wigner
+// tables hx_cl2corr / hx_corr2cl keep for their last lmax (4 (lmax + 1) ceil64(lmax + 1) doubles: 1.2 GB at lmax 6144, 4.9 GB at 12288).
+// The next call allocates again.
 extern "C" int hx_release_caches(void)
 {
     if (rt().ready) (void)hipStreamSynchronize(rt().stream);
     mix_cache_drop();
     alm2cl_drop_cache();
+    corr_cache_drop();
     return HX_OK;
 }
 

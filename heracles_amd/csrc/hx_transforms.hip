@@ -16,6 +16,12 @@ namespace hx {
 // T[ix][l][k]: ix 0: P_l, 1: d22, 2: d2m2, 3: d20 (zero for l < 2), k < n, row stride kpad
 __global__ void k_corr_tables(int lmax, int n, int kpad, const double *__restrict__ x, double *__restrict__ T)
 {
+    // Every product and sum rounds on its own, as in the reference's numpy (and the oracle's plain C): towards |x| -> 1 the closed forms
+    // below amplify the rounding of P_l, P_l' by their cancellation, so a recursion contracted to FMAs lands on another draw of that
+    // noise -- at the last node of n = 127 a white spectrum's xi- came out 23x further from the truth than the reference's formulas
+    // in plain double (3.9e-11 against 1.7e-12; elsewhere the contracted draw is as often the better one).  Uncontracted, the tables are
+    // the reference's arithmetic to the bit for equal nodes (tests/test_gpu_corr_stage.py::test_block_and_stride_edges[126]).
+#pragma clang fp contract(off)
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const long long sl = kpad, st = (long long)(lmax + 1) * kpad;
@@ -119,6 +125,7 @@ static int corr_tables(int lmax, CorrCache &c)
 {
     if (c.lmax == lmax && c.T.p) return HX_OK;
     const int n = lmax + 1, kpad = (n + 63) / 64 * 64;
+    c.lmax = -1;  // (a build that fails half-way leaves no size behind that the buffers no longer hold)
     HX_TRY(c.x.alloc(sizeof(double) * n));
     HX_TRY(c.w.alloc(sizeof(double) * n));
     HX_TRY(c.T.alloc(sizeof(double) * (size_t)4 * (lmax + 1) * kpad));
@@ -138,6 +145,17 @@ static CorrCache &corr_cache()
 {
     static CorrCache c;
     return c;
+}
+
+// hx_release_caches: the nodes, weights and the four tables of the last lmax (4 (lmax + 1) kpad doubles: 1.2 GB at lmax 6144)
+void corr_cache_drop()
+{
+    CorrCache &c = corr_cache();
+    c.x.release();
+    c.w.release();
+    c.T.release();
+    c.lmax = -1;
+    c.n = c.kpad = 0;
 }
 
 }  // namespace hx

@@ -194,7 +194,9 @@ int hx_mixmat_eb(const double *cl, int ncl, int l1max, int l2max, int l3max, dou
 int hx_mixmat_release(void);
 /* Everything the library keeps in HBM between calls OUTSIDE a plan or a context -- none of it is counted by hx_plan_scratch_bytes: the
  * cache of hx_mixmat / hx_mixmat_eb / hx_mixmat_batch (above; its staging buffer of a host destination also serves hx_mixctx_apply and
- * outlives hx_mixctx_destroy) and the tables, partial sums and staging buffer hx_alm2cl_pairs keeps (<= 512 MB).  A long-lived host
+ * outlives hx_mixctx_destroy), the tables, partial sums and staging buffer hx_alm2cl_pairs keeps (<= 512 MB), and the Gauss-Legendre
+ * nodes, weights and four Wigner tables hx_cl2corr / hx_corr2cl keep for their last lmax (4 (lmax + 1) ceil64(lmax + 1) doubles: 1.2 GB
+ * at lmax 6144, 4.9 GB at 12288; naturalspice runs them at the mask's band limit).  A long-lived host
  * process of the reference's loops (heracles/twopoint.py:173-299, :316-401) calls this between stages to hand the HBM back. */
 int hx_release_caches(void);
 /* ---- FITS wire format of maps and alms (heracles/io.py:128-218, "next" row) ------------------------------------

@@ -73,6 +73,37 @@ def test_dict_transforms_and_naturalspice(host_kernels, golden):
             np.testing.assert_array_equal(res[k].ell, ell)
 
 
+def test_dict_transforms_and_naturalspice_at_256_512(host_kernels):
+    """The same drivers with data at lmax 256 and masks at lmax 512 (apodised polar caps), against the reference's results of
+    tests/golden/make_golden_transforms.py: the dict-level transforms within 1.5x the deviation the generator measured for this very
+    path (oracle stubs; the reference's side is numpy's leggauss), naturalspice in the tolerance form of the L = 24 case."""
+    from corr_reference import dev_back, dev_rel
+
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_transforms.npz"))
+    L, Lm = 256, 512
+    ell, ellm = np.arange(L + 1), np.arange(Lm + 1)
+    keys = {("POS", "POS", 0, 0): (0, 0), ("POS", "SHE", 0, 0): (0, 2), ("SHE", "SHE", 0, 0): (2, 2)}
+    d = {k: hx.Result(np.array(g[f"dict/d/{key_str(k)}"]), spin=s, axis=-1, ell=ell) for k, s in keys.items()}
+    wd = hx.cl2corr(d)
+    back = hx.corr2cl({k: hx.Result(np.array(g[f"dict/wd/{key_str(k)}"]), spin=s, axis=-1, ell=wd[k].ell) for k, s in keys.items()})
+    for k in d:
+        ks = key_str(k)
+        assert dev_rel(wd[k].array, g[f"dict/wd/{ks}"]) <= 1.5 * g[f"dict/dev_wd/{ks}"]
+        assert dev_back(back[k].array, g[f"dict/back/{ks}"]) <= 1.5 * g[f"dict/dev_back/{ks}"]
+        assert type(wd[k]) is hx.Result and wd[k].spin == keys[k]
+    fields = {"POS": types.SimpleNamespace(mask="VIS", spin=0), "SHE": types.SimpleNamespace(mask="WHT", spin=2)}
+    for tag, tm in (("default", None), ("theta30", 30.0)):
+        m = {k: hx.Result(np.array(g[f"ns/m/{key_str(k)}"]), spin=(0, 0), axis=-1, ell=ellm)
+             for k in (("VIS", "VIS", 0, 0), ("VIS", "WHT", 0, 0), ("WHT", "WHT", 0, 0))}
+        with np.errstate(over="ignore"):  # (the damping factor overflows to inf where the mask's xi vanishes: xi_d / inf = 0, as in the reference)
+            res = hx.naturalspice(d, m, fields, theta_max=tm)
+        for k in d:
+            ref = g[f"ns/{tag}/{key_str(k)}"]
+            print(f"naturalspice {tag} {key_str(k)}: max |d| / max |ref| = {dev_rel(res[k].array, ref):.2e}")
+            np.testing.assert_allclose(res[k].array, ref, rtol=1e-6, atol=1e-9 * np.abs(ref).max())
+            np.testing.assert_array_equal(res[k].ell, ell)
+
+
 def test_invert_and_apply_mixing_matrix(host_kernels):
     g = np.load(os.path.join(ROOT, "tests", "golden", "reference_mixing.npz"))
     spins = {"POS|POS|0|0": (0, 0), "POS|SHE|0|1": (0, 2), "SHE|SHE|1|1": (2, 2)}
