@@ -27,6 +27,7 @@ from .discrete import HipDiscreteMapper, PointSHT, alm_resample, get_point_sht
 from .jackknife import RegionAlms, jackknife_cls, region_alms
 from .mapper import HipHealpixMapper
 from .catalog import ArrayCatalog, CatalogView, FootprintFilter, InvalidValueFilter
+from .fitscatalog import FitsCatalog
 from .fields import (
     ComplexField,
     Ellipticities,
@@ -68,6 +69,6 @@ __all__ = [
     "pinned_empty", "release_caches", "mixmat_release", "split_requests", "binned", "BinPlan", "MixmatContext", "jackknife_cls", "region_alms", "RegionAlms", "transform", "read_vmap", "apply_mixing_matrix", "invert_mixing_matrix",
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
-    "map_catalogs", "ArrayCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
+    "map_catalogs", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
     "Visibility", "Weights", "get_masks",
 ]

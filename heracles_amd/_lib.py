@@ -28,7 +28,7 @@ SYMBOLS = (
     "hx_profile_enable", "hx_profile_reset", "hx_profile_get", "hx_plan_create", "hx_set_max_lds_fft",
     "hx_plan_destroy", "hx_plan_scratch_bytes", "hx_plan_release_scratch", "hx_set_scratch_budget", "hx_plan_last_chunks", "hx_plan_mfma_flops", "hx_plan_executed_flops", "hx_executed_flops", "hx_measure_peaks", "hx_measured_mfma_clock", "hx_map2alm", "hx_map2alm_multi", "hx_map2alm_list", "hx_alm2map", "hx_copy",
     "hx_alm2cl_pairs", "hx_alm2cl_pairs_range", "hx_gauss_legendre", "hx_gauss_legendre_dd", "hx_wigner_d_table", "hx_mixmat",
-    "hx_mixmat_eb", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_cl2corr", "hx_corr2cl", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64",
+    "hx_mixmat_eb", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_cl2corr", "hx_corr2cl", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64", "hx_fits_unpack_columns",
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
     "hx_pixel_weights_size", "hx_pixel_weights_expand",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
@@ -122,6 +122,7 @@ def load():
         L.hx_alm_subtract.argtypes = [C.c_int64, dp, i, vp, dp]
         L.hx_fits_unpack_f64.argtypes = [C.c_int64, i, i, C.c_int64, C.c_int64, C.c_int64, dp, dp]
         L.hx_fits_pack_f64.argtypes = [C.c_int64, i, i, C.c_int64, C.c_int64, C.c_int64, dp, dp]
+        L.hx_fits_unpack_columns.argtypes = [C.c_int64, C.c_int64, i, vp, C.c_char_p, vp, vp, dp, vp, i]
         L.hx_pointsht_create.argtypes = [i, C.c_double]
         L.hx_pointsht_create.restype = vp
         L.hx_pointsht_destroy.argtypes = [vp]
@@ -195,11 +196,12 @@ def init(device: int | None = None):
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) % max(L.hx_device_count(), 1)
     check(L.hx_init(int(device)))
-    global _inited
-    _inited = True
+    global _inited, _device
+    _inited, _device = True, int(device)
 
 
 _inited = False
+_device = None
 
 
 def ensure_init():
@@ -208,6 +210,12 @@ def ensure_init():
     if not _inited:
         init(None)
         _inited = True
+
+
+def device() -> int:
+    """Index of the device the library runs on (initialising it if need be)."""
+    ensure_init()
+    return _device
 
 
 def device_count() -> int:

@@ -3,10 +3,12 @@
 ``ArrayCatalog`` wraps a numpy structured array, or a mapping from column name to a 1-D numpy array or a contiguous float64 CUDA
 tensor.  Pages are slices of the columns: device columns stay in HBM and reach the kernels without a copy.  Any other object with the
 same protocol -- iteration over pages with ``get`` / ``[col]`` / ``size`` / ``delete``, and ``visibility``, ``fsky``, ``metadata``,
-``size``, ``page_size`` -- works as well, a ``heracles.FitsCatalog`` among them.
+``size``, ``page_size`` -- works as well, a ``heracles.FitsCatalog`` among them.  ``heracles_amd.fitscatalog.FitsCatalog`` is this
+class with a FITS table as its source of pages.
 
 ``where`` / ``[]`` give ``CatalogView``s (heracles/catalog/base.py:204-310) and ``add_filter`` takes ``InvalidValueFilter`` and
-``FootprintFilter`` (heracles/catalog/filters.py); ``map_catalogs`` maps the views of one ``ArrayCatalog`` in one pass over its pages.
+``FootprintFilter`` (heracles/catalog/filters.py); ``map_catalogs`` maps the views of one ``ArrayCatalog`` in one pass over its pages
+(``_column_dtypes`` / ``_page_columns`` are the page source it reads).
 """
 
 from __future__ import annotations
@@ -143,32 +145,12 @@ class CatalogPage:
         self._size = len(next(iter(self._data.values()))) if self._data else 0
 
 
-class ArrayCatalog:
-    """Catalogue of in-memory columns, read in pages of ``page_size`` rows.  ``fsky`` is the mean of the visibility, if one is set
-    (heracles/catalog/base.py:36-44), else ``None``."""
+class _CatalogBase:
+    """What ``ArrayCatalog`` and ``FitsCatalog`` share: ``page_size``, ``visibility`` and ``fsky``, the metadata, the filters, and ``[]`` /
+    iteration in terms of the ``where`` and ``select`` each of them defines.  ``map_catalogs`` maps the views of either in one pass, through
+    ``_column_dtypes()`` and ``_page_columns(start, stop)``."""
 
-    default_page_size = 1_000_000
-
-    def __init__(self, data, *, page_size=default_page_size, visibility=None, metadata=None):
-        if isinstance(data, np.ndarray):
-            if data.dtype.names is None:
-                raise TypeError("ArrayCatalog: a numpy array must be structured (one field per column)")
-            cols = {name: data[name] for name in data.dtype.names}
-        else:
-            cols = dict(data)
-        for name, v in cols.items():
-            if _is_tensor(v):
-                import torch
-
-                if v.ndim != 1 or v.dtype != torch.float64 or not v.is_contiguous():
-                    raise ValueError(f"column {name!r}: device columns must be 1-D contiguous float64 tensors")
-            elif np.ndim(v) != 1:
-                raise ValueError(f"column {name!r} is not 1-D")
-        sizes = {len(v) for v in cols.values()}
-        if len(sizes) > 1:
-            raise ValueError("inconsistent row length")
-        self._cols = cols
-        self._size = sizes.pop() if sizes else 0
+    def _setup(self, page_size, visibility, metadata):
         self.page_size = int(page_size)
         self.visibility = visibility
         self._metadata = {"catalog": None, **dict(metadata or {})}
@@ -183,14 +165,6 @@ class ArrayCatalog:
         if value < 1:
             raise ValueError("page_size must be positive")
         self._page_size = int(value)
-
-    @property
-    def names(self):
-        return list(self._cols)
-
-    @property
-    def size(self):
-        return self._size
 
     @property
     def metadata(self):
@@ -231,6 +205,49 @@ class ArrayCatalog:
     def add_filter(self, filt):
         self._filters.append(filt)
 
+    def __getitem__(self, where):
+        return self.where(where)
+
+    def __iter__(self):
+        yield from self.select(None)
+
+
+class ArrayCatalog(_CatalogBase):
+    """Catalogue of in-memory columns, read in pages of ``page_size`` rows.  ``fsky`` is the mean of the visibility, if one is set
+    (heracles/catalog/base.py:36-44), else ``None``."""
+
+    default_page_size = 1_000_000
+
+    def __init__(self, data, *, page_size=default_page_size, visibility=None, metadata=None):
+        if isinstance(data, np.ndarray):
+            if data.dtype.names is None:
+                raise TypeError("ArrayCatalog: a numpy array must be structured (one field per column)")
+            cols = {name: data[name] for name in data.dtype.names}
+        else:
+            cols = dict(data)
+        for name, v in cols.items():
+            if _is_tensor(v):
+                import torch
+
+                if v.ndim != 1 or v.dtype != torch.float64 or not v.is_contiguous():
+                    raise ValueError(f"column {name!r}: device columns must be 1-D contiguous float64 tensors")
+            elif np.ndim(v) != 1:
+                raise ValueError(f"column {name!r} is not 1-D")
+        sizes = {len(v) for v in cols.values()}
+        if len(sizes) > 1:
+            raise ValueError("inconsistent row length")
+        self._cols = cols
+        self._size = sizes.pop() if sizes else 0
+        self._setup(page_size, visibility, metadata)
+
+    @property
+    def names(self):
+        return list(self._cols)
+
+    @property
+    def size(self):
+        return self._size
+
     def _join(self, *where):
         """Selections join lazily: a flat tuple of terms, ANDed row by row."""
         joined = _flatten(where)
@@ -245,8 +262,14 @@ class ArrayCatalog:
             _check_selection(selection, self._size)
         return CatalogView(self, selection, visibility)
 
-    def __getitem__(self, where):
-        return self.where(where)
+    # the page source ``map_catalogs`` reads when it maps the views of one base in one pass
+    def _column_dtypes(self):
+        """{column: dtype} of the columns as the pages hold them (device columns are float64)."""
+        return {name: (np.float64 if _is_tensor(v) else np.asarray(v).dtype) for name, v in self._cols.items()}
+
+    def _page_columns(self, start, stop):
+        """{column: rows [start, stop)} before any selection or filter."""
+        return {name: v[start:stop] for name, v in self._cols.items()}
 
     def _mask(self, selection, start, stop):
         """The rows [start, stop) of the catalogue that ``selection`` keeps, or ``None`` for all."""
@@ -312,9 +335,6 @@ class ArrayCatalog:
             for filt in self._filters:
                 filt(page)
             yield page
-
-    def __iter__(self):
-        yield from self.select(None)
 
 
 class CatalogView:

@@ -12,7 +12,8 @@ row-major payload), and the payload conversion -- byte swap + (de)interleave of 
 Files written here carry the cards ``fitsio`` writes for the same call (HIERARCH convention for the ``META`` keys,
 ``TDIMn`` for vector columns) and are laid out so that the reference's own ``read_maps`` / ``read_alms`` read them;
 files written by the reference (any 'D'-column table, vector columns included) are read.  Parity with fitsio-written
-files is pinned on the FITS standard only: the reference tree holds no FITS fixture and fitsio is absent here.
+files is pinned on the FITS standard only: the reference tree holds no FITS fixture and fitsio is absent here.  The same holds
+for the catalogue tables ``heracles_amd.fitscatalog.FitsCatalog`` reads with this module's header parser.
 """
 
 from __future__ import annotations

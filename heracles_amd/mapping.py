@@ -486,18 +486,17 @@ def _compile_predicate(expr, dtypes):
 
 
 def _dtypes(base):
-    import torch
-
-    return {name: (np.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype) for name, v in base._cols.items()}
+    """{column: dtype} of the base's page columns (its page source: ``ArrayCatalog`` and ``FitsCatalog`` both provide it)."""
+    return base._column_dtypes()
 
 
 def _sel_base(catalog):
-    """The base ``ArrayCatalog`` whose one-pass group ``catalog`` joins, or None for the per-catalogue path: a ``heracles_amd`` view, or
+    """The base ``ArrayCatalog`` or ``FitsCatalog`` whose one-pass group ``catalog`` joins, or None for the per-catalogue path: a ``heracles_amd`` view, or
     its base itself, whose filters are all of the two known types."""
-    from .catalog import ArrayCatalog, CatalogView, FootprintFilter, InvalidValueFilter
+    from .catalog import CatalogView, FootprintFilter, InvalidValueFilter, _CatalogBase
 
     base = catalog.base if isinstance(catalog, CatalogView) else catalog
-    if not isinstance(base, ArrayCatalog) or not isinstance(catalog, (ArrayCatalog, CatalogView)):
+    if not isinstance(base, _CatalogBase) or not isinstance(catalog, (_CatalogBase, CatalogView)):
         return None
     if len(base.filters) > _MAX_FILTERS or any(type(f) not in (InvalidValueFilter, FootprintFilter) for f in base.filters):
         return None
@@ -654,7 +653,7 @@ def _map_selections(base, entries, terms, device, device_out):
         try:
             for start in range(0, base.size, cap):
                 stop = min(base.size, start + cap)
-                page = {c: base._cols[c][start:stop] for c in base._cols}
+                page = base._page_columns(start, stop)
                 view = CatalogPage(page)
                 arrays = [_column(view[c], device) for c in cols]
                 masks = [[_chunk_mask(t, page, start, stop) for t in m] for _, m in terms]

@@ -208,6 +208,25 @@ int hx_release_caches(void);
 int hx_fits_unpack_f64(int64_t nrows, int nc1, int nc2, int64_t s1, int64_t s2, int64_t srow, const void *table, double *array);
 int hx_fits_pack_f64(int64_t nrows, int nc1, int nc2, int64_t s1, int64_t s2, int64_t srow, const double *array, void *table);
 
+/* ---- catalogue tables (heracles/catalog/fits.py: the columns a FitsCatalog page holds) ---------------------------------------
+ * One page of a FITS binary table -- `nrows` records of `width` (NAXIS1) bytes, big-endian, as they are in the file -- to `ncols`
+ * native float64 arrays of `nrows` values, one per selected column, in one pass on the GPU.  Column c is the scalar field of TFORM
+ * letter types[c] at byte offsets[c] of the record:
+ *   'L' ('T' -> 1.0, any other byte -> 0.0), 'B' (unsigned byte), 'I', 'J', 'K' (signed 16 / 32 / 64 bit), 'E', 'D'.
+ * Integer -> f64 and f32 -> f64 are exact; 'K' values beyond +-2^53 round to nearest even, as a C cast does.  Where tscal[c] != 1 or
+ * tzero[c] != 0 the value is stored * tscal + tzero with the product rounded before the sum (no fused multiply-add): numpy's result,
+ * and exact for the unsigned conventions ('I' + 32768, 'J' + 2147483648, 'B' - 128).  tscal / tzero may be NULL (no scaling).  TNULL
+ * is not interpreted (fitsio does not by default either).  Fields that are not listed -- strings, vectors, descriptors -- are skipped
+ * by offset.  Nothing is assumed of `width` (it may be odd) or of the alignment of `table`, a record or a field.
+ * `table` (nrows * width bytes) host or device (a page-locked host table is uploaded by one asynchronous copy ahead of the kernel);
+ * `columns`: ncols DEVICE pointers.  At most HX_FITS_MAX_COLUMNS columns per call.  A block stages min(1024, 48 KiB / width) records
+ * (rounded down to a multiple of 64 when at least 64) in LDS; records wider than 48 KiB, and every call with HX_FITS_DIRECT in `flags`,
+ * are read field by field from global memory instead (same results; the flag exists for timing and testing the two kernels). */
+#define HX_FITS_MAX_COLUMNS 64
+#define HX_FITS_DIRECT 1
+int hx_fits_unpack_columns(int64_t nrows, int64_t width, int ncols, const int64_t *offsets, const char *types, const double *tscal,
+                           const double *tzero, const void *table, double *const *columns, int flags);
+
 /* ---- jackknife loop in HBM (heracles/dices/jackknife.py:93-248, "next" row) ------------------------------------
  * Region maps (jackknife.py:253-263: every pixel outside region k set to zero) and delete-k alms (jackknife.py:222-233,
  * :298-304: full alms minus the sum of the deleted regions' alms) without leaving the device.                      */
