@@ -26,7 +26,7 @@
 namespace hx {
 using namespace hxfft;
 
-// tuning knobs (tools/build_valu_variants.sh)
+// tuning knobs (constants since round 6; as build switches: tools/build_variant.sh --switches)
 constexpr int VALU_R0 = 8;
 constexpr int VALU_R2 = 6;
 constexpr int VALU_LB0 = 8;
@@ -172,7 +172,7 @@ __device__ __forceinline__ void wave_reduce(double (&v)[N], int lane)
 // =====================================================================================
 // the kernel: one wave per task (m, ring group)
 // =====================================================================================
-constexpr int VALU_WAVES = 1;  // waves per SIMD the register allocation is made for (tuning knob of tools/build_valu_variants.sh)
+constexpr int VALU_WAVES = 1;  // waves per SIMD the register allocation is made for (tuning knob: tools/build_variant.sh --switches)
 constexpr int VALU_CHK = 64;  // l between two promotion / liveness checks of a wave (a multiple of LB)
 template <int SPIN>
 __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, const double2 *__restrict__ coefn, const double *__restrict__ alphan)

@@ -1,6 +1,27 @@
-// hx_sht_common.h -- plan structure, device-side plan view and scaled-arithmetic helpers
-// shared by hx_sht.hip (plan, ring Fourier stage, synthesis, C ABI) and hx_analysis.hip
-// (Legendre analysis on FP64 MFMA).
+// hx_sht_common.h -- HEALPix spherical harmonic transforms for gfx950: plan structure, device-side plan view and
+// scaled-arithmetic helpers shared by the translation units of the transforms -- hx_plan.hip (plan and band-limit tables),
+// hx_ring_fft.hip (ring Fourier stage), hx_analysis.hip (Legendre analysis on FP64 MFMA), hx_legendre_valu.hip and
+// hx_synth_duo.hip (vector-unit kernels, batched synthesis), hx_synthesis.hip (alm2map), hx_map2alm.hip (map2alm entry points).
+//
+// Replaces healpy.map2alm / alm2map as called from heracles/healpy.py:183-189 (spin 0 and
+// spin 2, RING-ordered maps, mmax == lmax).
+//
+// Pipeline of one analysis sweep (<= 16 map components):
+//   1. k_ring_subdft       (hx_ring_fft.hip) ring Fourier stage.  A north/south ring pair is packed as
+//                          z = f_N + i f_S and transformed as one complex DFT of length
+//                          4n, split radix-4 (DIF) into four length-n DFTs; a work item is ONE of
+//                          them, run entirely in LDS (fused radix-8 / radix-16 passes on a padded
+//                          buffer; plain FFT for n = 2^k, Bluestein otherwise), the four items of a
+//                          ring pair in four work-groups of one XCD so that they share its L2.
+//   2. k_fourier_combine   (hx_analysis.hip) un-packs N/S, applies ring phase / quadrature weight, forms
+//                          the parity combinations and writes the MFMA B-operand layout
+//                          F[m][ring pair][parity][op][columns].
+//   3. k_legendre_duo      (hx_analysis.hip) Legendre / Wigner-d stage: lanes = ring pairs run the
+//                          three-term recursion in l; tiles of lambda_lm go through LDS into A operands
+//                          of v_mfma_f64_16x16x4_f64, which contracts over rings against the F operands
+//                          held in registers; one work-group per m adds its ring groups in place.
+//   4. k_alm_reduce        (hx_analysis.hip) rows -> alm layout (x fl); for the small-batch kernels also the
+//                          fixed-order sum of the ring-group partials.
 #pragma once
 #include <map>
 #include <vector>
@@ -355,11 +376,18 @@ struct hx_plan {
 };
 
 namespace hx {
-// hx_sht.hip
+// hx_plan.hip
 hx_plan *plan_create_equiangular(int N, int lmax);
 int ensure_rec2(hx_plan *pl);
+// hx_ring_fft.hip
+int ring_fft_plan_init(hx_plan *pl, const std::vector<int> &nsub, const std::vector<long long> &sN, const std::vector<long long> &sS);  // (hx_plan_create, behind the band-limit tables)
 int launch_ring_subdft_maps(hx_plan *pl, int nb, const double *d_maps, const double *d_pw, double2 *Y, int rp_lo = 0, int rp_hi = 0x7fffffff);  // ring pairs [rp_lo, rp_hi) only
+int launch_ring_subdft_spectra(hx_plan *pl, int nc, const double2 *zin, double *pixout, const double *ref);  // spectra -> pixels, or the residual ref - pixels
 int classify_pixel_weights(hx_plan *pl, const double *d_pw);
+// hx_synthesis.hip
+int synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, double *d_maps, const double *d_ref);  // d_ref: maps <- ref - synthesised
+// hx_map2alm.hip
+int check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b);
 // hx_analysis.hip
 int build_tasks(hx_plan *pl, int spin);
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,

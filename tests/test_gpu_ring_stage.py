@@ -35,7 +35,7 @@ def _lds_slots(M):
 
 
 def fft_class(n, cap=8192):
-    """The kernel launch_subdft_classes gives a ring pair with sub-DFTs of length n (hx_sht.hip plan creation)."""
+    """The kernel a ring pair with sub-DFTs of length n runs on (hx_ring_fft.hip: ring_class_is_pair, ring_fft_plan_init)."""
     M = fft_size_for(n)
     if M == n:
         pair = 16 <= M <= cap and (2 * _lds_slots(M) + (4 * M) // 64 + 1 + 64) * 16 + 4096 <= 160 * 1024

@@ -1,9 +1,4 @@
-# same-device A/B of HX_DUO_GAP builds (tools/build_variant.sh hx_analysis.hip g<N> "-DHX_DUO_GAP=<N>"): tools/ab_gap.sh "2 20" g6 g10 ...
-spec=${1:-"2 20"}; shift
-for rep in 1 2; do
-for t in default "$@"; do
-lib=""; [ "$t" != default ] && lib=$PWD/tools/bin/libhxsht_$t.so
-set -- $spec "$@"
-env HX_LIBRARY=$lib NSIDE=4096 LMAX=6144 SPIN=$1 NCOMP=$2 python tools/leg_only.py 2>/dev/null | sed "s|^|$t: |" | cut -c1-140
-shift 2
-done; done
+#!/bin/sh
+# Retired: HX_DUO_GAP became constants in round 6, so this script built (or compared) identical libraries.
+echo "ab_gap.sh: HX_DUO_GAP left the sources in round 6; use tools/build_variant.sh --switches hx_analysis.hip g<N> \"-DHX_DUO_GAP=<N>\", then tools/ab_lib.sh default g<N> \"2 20\"" >&2
+exit 1

@@ -1,6 +1,6 @@
 """Calibration of the per-block entry thresholds of k_legendre_duo / k_synth_duo (set_mode): for every 32-l block b of an order m, the margin
 E_b (bits below 2^-100) a chain must have at the entry of the block so that no value of lambda above 2^-75 is reached inside it by a ring
-that is skipped.  Emulates the normalised recursions of hx_sht.hip (k_init_norm0 / k_init_norm2) in long double.  CPU only.
+that is skipped.  Emulates the normalised recursions of hx_plan.hip (k_init_norm0 / k_init_norm2) in long double.  CPU only.
 
     python tools/calibrate_dead_blocks.py [BLK [LMAX [NSIDE]]]      BLK: 32 (k_legendre_duo) or 16 (k_synth_duo); default 32 6144
 

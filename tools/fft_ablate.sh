@@ -1,12 +1,4 @@
-#!/bin/bash
-# builds libhxsht variants with phases of k_ring_subdft removed (HX_FFT_ABL bits: 1 no sincos,
-# 2 no forward FFT, 4 no filter read, 8 no inverse FFT, 16 no pixel loads) and times the ring
-# Fourier stage of one 8-component map2alm at nside 4096.  Results are wrong by design.
-set -e
-cd "$(dirname "$0")/../heracles_amd/csrc"
-OBJS=$(ls *.o | grep -v "^hx_sht.o")
-mkdir -p ../../tools/bin
-for a in "$@"; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DHX_FFT_ABL=$a -c hx_sht.hip -o /tmp/hx_sht_abl$a.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/bin/libhxsht_fa$a.so $OBJS /tmp/hx_sht_abl$a.o
-done
+#!/bin/sh
+# Retired: HX_FFT_ABL became constants in round 6, so this script built (or compared) identical libraries.
+echo "fft_ablate.sh: HX_FFT_ABL left the sources in round 6; use tools/build_variant.sh --switches hx_sht.hip fa<bits> \"-DHX_FFT_ABL=<bits>\"" >&2
+exit 1
