@@ -40,7 +40,7 @@ from .fields import (
     Weights,
     get_masks,
 )
-from .mapping import map_catalogs, transform
+from .mapping import catalog_alms, map_catalogs, transform
 from .sht import Plan, get_plan
 from .transforms import cl2corr, corr2cl, gauss_legendre, wigner_d_table
 from .fits import read_vmap
@@ -69,6 +69,6 @@ __all__ = [
     "pinned_empty", "release_caches", "mixmat_release", "split_requests", "binned", "BinPlan", "MixmatContext", "jackknife_cls", "region_alms", "RegionAlms", "transform", "read_vmap", "apply_mixing_matrix", "invert_mixing_matrix",
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
-    "map_catalogs", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
+    "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
     "Visibility", "Weights", "get_masks",
 ]

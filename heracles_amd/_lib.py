@@ -34,6 +34,7 @@ SYMBOLS = (
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
+    "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
     "hx_catmap_create_sel", "hx_catmap_page_sel", "hx_catmap_moments_sel", "hx_catmap_finish_sel", "hx_catmap_destroy_sel",
 )
 
@@ -151,6 +152,13 @@ def load():
         L.hx_catmap_finish.argtypes = [vp, i, C.c_double, dp]
         L.hx_catmap_destroy.argtypes = [vp]
         L.hx_catmap_destroy.restype = None
+        L.hx_catalm_create.restype = vp
+        L.hx_catalm_create.argtypes = [C.c_int64, i, i, vp, vp]
+        L.hx_catalm_page.argtypes = [vp, C.c_int64, vp]
+        L.hx_catalm_moments.argtypes = [vp, dp, dp]
+        L.hx_catalm_finish.argtypes = [vp, i, i, C.c_double, dp, dp]
+        L.hx_catalm_destroy.argtypes = [vp]
+        L.hx_catalm_destroy.restype = None
         L.hx_catmap_create_sel.restype = vp
         L.hx_catmap_create_sel.argtypes = [C.c_int64, i, i, vp, i, i, vp, vp, i, vp, vp, vp]
         L.hx_catmap_page_sel.argtypes = [vp, C.c_int64, vp, vp]

@@ -27,8 +27,10 @@ def _is_tensor(x):
 
 
 def _fsky_of(vis):
-    """heracles/catalog/base.py:36-44 for a map: the mean of the visibility."""
+    """heracles/catalog/base.py:36-44: the mean of a visibility map; a_00 / sqrt(4 pi) of visibility alms (a complex array)."""
     if _is_tensor(vis):
+        if vis.is_complex():
+            return float(vis[0].real) / (4 * np.pi) ** 0.5
         return float(vis.mean())
     if np.iscomplexobj(vis):
         return vis[0].real / (4 * np.pi) ** 0.5
@@ -177,11 +179,7 @@ class _CatalogBase:
     @property
     def fsky(self):
         vis = self.visibility
-        if vis is None:
-            return None
-        if _is_tensor(vis):
-            return float(vis.mean())
-        return vis.mean()
+        return None if vis is None else _fsky_of(vis)
 
     @property
     def base(self):

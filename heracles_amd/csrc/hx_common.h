@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -122,5 +123,20 @@ void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner table
 
 // Gauss-Legendre nodes/weights into device arrays (hx_mixmat.hip)
 int launch_gauss_legendre(int n, double *d_x, double *d_w, double *d_xlo = nullptr);  // d_xlo: node k = x[k] + xlo[k] (see k_gauss_legendre)
+
+// The two halves of hx_pointsht_adjoint (hx_nufft.hip), for callers that keep grids resident (hx_catalm, hx_mapper.hip).
+// Half one: pointsht_order picks the spreading path for n points (tiles from 300000 points, HX_NUFFT_TILES forces it) and sorts them
+// by tile when that path is taken -- once for every component spread from these points; pointsht_spread_one ADDS one component
+// (val[n] at loc[n] = (theta, phi)) to grid [n1][n1], without clearing it.  The order lives in the buffers of `ps` until its next call.
+// Half two: pointsht_grids_to_alm runs the three FFT stages on the grid grid_of(c) hands out for component c, then the Legendre
+// analysis: d_alm [ncomp][nlm] on the device.
+struct PointOrder {
+    bool tiles = false;
+    unsigned *key = nullptr, *idx = nullptr;  // sorted (tile, point index) pairs
+};
+using GridOf = std::function<int(int c, const double **grid)>;
+int pointsht_order(hx_pointsht *ps, int64_t npoints, const double2 *loc, PointOrder *o);
+int pointsht_spread_one(hx_pointsht *ps, const PointOrder &o, int64_t npoints, const double2 *loc, const double *val, double *grid);
+int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &grid_of, double2 *d_alm);
 
 }  // namespace hx

@@ -637,6 +637,55 @@ __device__ __forceinline__ GroupStep group_step(const CatCore &a, int g, long lo
     return s;
 }
 
+// Every field on row j, for the prepare kernels of hx_catmap and hx_catalm: field_step, the NaN counters (nan [nfield][5]), the
+// thread's moment sums m and which groups have a field that keeps the row.
+template <int NF>
+__device__ __forceinline__ void fields_step(const CatCore &a, long long j, double (&m)[NF][4], bool (&kept)[kCatG], unsigned long long *nan)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int g = 0; g < kCatG; ++g) kept[g] = false;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const FieldStep s = field_step(a, f, j);
+        if (s.keep) {
+#pragma unroll
+            for (int g = 0; g < kCatG; ++g)
+                if (g == a.grp[f]) kept[g] = true;
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                if ((s.nan >> k) & 1u) atomicAdd(nan + 5 * f + k, 1ULL);
+            // (a dropped row's contributions are +0.0 and adding them would leave the sums as they are, bit for bit: the sums start at
+            // +0.0 and never become -0.0.  Adding under the branch keeps the kernel at 8 VGPRs per field instead of 16.)
+            m[f][0] += s.n;
+            m[f][1] += s.w;
+            m[f][2] += s.w2;
+            m[f][3] += s.v2;
+        }
+    }
+}
+
+// per-block partial moments: fixed-shape wave and block reductions into slab[blockIdx.x][NF * 4]
+template <int NF>
+__device__ __forceinline__ void block_moments(const double (&m)[NF][4], double *slab)
+{
+#pragma clang fp contract(off)
+    __shared__ double part[4][kCatF * 4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double s = wave_sum(m[f][k]);
+            if (lane == 0) part[wv][f * 4 + k] = s;
+        }
+    __syncthreads();
+    if (threadIdx.x < NF * 4) {
+        const int t = threadIdx.x;
+        slab[(long long)blockIdx.x * NF * 4 + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+    }
+}
+
 // NF = the number of fields, a template argument so that only their moments occupy registers
 template <int NF>
 __global__ __launch_bounds__(256) void k_cat_prepare(long long n, CatArgs a)
@@ -650,26 +699,7 @@ __global__ __launch_bounds__(256) void k_cat_prepare(long long n, CatArgs a)
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
         bool kept[kCatG];
-#pragma unroll
-        for (int g = 0; g < kCatG; ++g) kept[g] = false;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const FieldStep s = field_step(a.c, f, j);
-            if (s.keep) {
-#pragma unroll
-                for (int g = 0; g < kCatG; ++g)
-                    if (g == a.c.grp[f]) kept[g] = true;
-#pragma unroll
-                for (int k = 0; k < 5; ++k)
-                    if ((s.nan >> k) & 1u) atomicAdd(a.nan + 5 * f + k, 1ULL);
-                // (a dropped row's contributions are +0.0 and adding them would leave the sums as they are, bit for bit: the sums start at
-                // +0.0 and never become -0.0.  Adding under the branch keeps the kernel at 8 VGPRs per field instead of 16.)
-                m[f][0] += s.n;
-                m[f][1] += s.w;
-                m[f][2] += s.w2;
-                m[f][3] += s.v2;
-            }
-        }
+        fields_step<NF>(a.c, j, m, kept, a.nan);
 #pragma unroll
         for (int g = 0; g < kCatG; ++g) {
             if (g >= a.c.ngroup) break;
@@ -679,21 +709,7 @@ __global__ __launch_bounds__(256) void k_cat_prepare(long long n, CatArgs a)
             a.ord[g][j] = (unsigned)j;
         }
     }
-    // per-block partial moments: fixed-shape wave and block reductions
-    __shared__ double part[4][kCatF * 4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int f = 0; f < NF; ++f)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double s = wave_sum(m[f][k]);
-            if (lane == 0) part[wv][f * 4 + k] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < NF * 4) {
-        const int t = threadIdx.x;
-        a.slab[(long long)blockIdx.x * NF * 4 + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-    }
+    block_moments<NF>(m, a.slab);
 }
 
 // acc[t] += sum over blocks of slab[b][t], b in order: the moments of the page added to the context's
@@ -704,6 +720,76 @@ __global__ __launch_bounds__(256) void k_cat_reduce(int nblocks, int width, cons
     double s = 0.0;
     for (int b = 0; b < nblocks; ++b) s += slab[(long long)b * width + t];
     acc[t] += s;
+}
+
+// ---- hx_catalm: the same page, prepared for the point transform (no pixels, no sort key) -----------------------------------------
+struct AlmArgs {
+    CatCore c;             // gnside[g]: the band limit of group g
+    double2 *loc[kCatG];   // per group: (theta, phi) of every row
+    unsigned long long *nan;   // [nfield][5]
+    unsigned long long *nbad;  // [ngroup]
+    double *slab;              // [gridDim.x][nfield * 4]
+};
+
+// One (lmax, lon, lat) group on one row: the point (theta, phi) = (radians(90 - lat), radians(lon % 360)) of
+// heracles/ducc.py:117-119, every operation rounded on its own (lat = -90 gives exactly M_PI, the largest colatitude the spread
+// takes).  Validity is group_step's rule without its 1e-5 of slack beyond the south pole, which the (theta, phi) grid has no cell
+// for: a latitude outside [-90, 90] or a non-finite coordinate is bad on a wanted row.  A row that adds nothing -- no field of the
+// group keeps it, or its position is invalid -- gets a ZERO VALUE (field_step writes 0 on a dropped row; k_catalm_prepare clears the
+// value rows of a bad one) at a harmless location: its own position when that is valid, else the equator.  The spread kernels skip a
+// zero value before any atomic, and a finite zero at a valid location is never counted as a bad point.
+struct PointStep {
+    double2 loc;
+    bool bad;
+};
+
+__device__ __forceinline__ PointStep point_step(const CatCore &a, int g, long long j, bool wanted)
+{
+#pragma clang fp contract(off)
+    const double lo = a.col[a.glon[g]][j], la = a.col[a.glat[g]][j];
+    const bool ok = isfinite(lo) && la >= -90.0 && la <= 90.0;
+    PointStep s{{kHalfPi, 0.0}, wanted && !ok};
+    if (ok) {
+        double r = fmod(lo, 360.0);  // numpy's %: the sign of the divisor
+        if (r < 0.0) r += 360.0;
+        s.loc.x = (90.0 - la) * kDeg2Rad;
+        s.loc.y = r * kDeg2Rad;
+    }
+    return s;
+}
+
+// k_cat_prepare for the point transform: field_step and the moment reduction as they are there (8 VGPRs of sums per field, NF a
+// template argument for the same reason); per group one double2 store instead of the key and the row index.
+template <int NF>
+__global__ __launch_bounds__(256) void k_catalm_prepare(long long n, AlmArgs a)
+{
+#pragma clang fp contract(off)
+    double m[NF][4];
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[f][k] = 0.0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        bool kept[kCatG];
+        fields_step<NF>(a.c, j, m, kept, a.nan);
+#pragma unroll
+        for (int g = 0; g < kCatG; ++g) {
+            if (g >= a.c.ngroup) break;
+            const PointStep s = point_step(a.c, g, j, kept[g]);
+            a.loc[g][j] = s.loc;
+            if (s.bad) {  // (rare, and an error for the caller: the row must still add nothing)
+                atomicAdd(a.nbad + g, 1ULL);
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+                    if (a.c.grp[f] == g) {
+                        a.c.val[f][j] = 0.0;
+                        if (a.c.kind[f] == HX_CAT_COMPLEX) a.c.val[f][a.c.cap + j] = 0.0;
+                    }
+            }
+        }
+    }
+    block_moments<NF>(m, a.slab);
 }
 
 // k_run_add for one value row and one map row, ending at the sentinel key npix: a pixel's run is added in catalogue order, starting
@@ -932,9 +1018,11 @@ struct CatBase {
 
 inline bool col_ok(int i, int ncols, bool need) { return i >= (need ? 0 : -1) && i < ncols; }
 
-// Validates the field descriptors, forms the (nside, lon, lat) groups and allocates the value rows; `who`: the entry point, for messages
+// Validates the field descriptors, forms the (resolution, lon, lat) groups and allocates the value rows; `who`: the entry point, for
+// messages.  The resolution (desc[1], kept in nside[] / gnside[]) is an nside in [1, 16384] for the map contexts, which pass their device
+// maps; hx_catalm passes maps = NULL (it owns its outputs) and res_lo / res_hi = the range of its lmax.
 int cat_fields_init(CatBase *c, CatCore &a, const char *who, int64_t page_size, int ncols, int nfields, const int *desc, int nsel,
-                    double *const *maps)
+                    double *const *maps, int res_lo = 1, int res_hi = 16384)
 {
     c->cap = a.cap = page_size;
     c->ncols = ncols;
@@ -945,19 +1033,19 @@ int cat_fields_init(CatBase *c, CatCore &a, const char *who, int64_t page_size, 
         const int kind = d[0], ns = d[1];
         const bool need_v = kind == HX_CAT_SCALAR || kind == HX_CAT_COMPLEX;
         bool maps_ok = true;
-        for (int s = 0; s < nsel; ++s) {
+        for (int s = 0; maps && s < nsel; ++s) {
             c->map[s * nfields + f] = maps[s * nfields + f];
             maps_ok = maps_ok && maps[s * nfields + f] && is_device_ptr(maps[s * nfields + f]);
         }
-        if (kind < HX_CAT_POSITIONS || kind > HX_CAT_WEIGHTS || !nside_ok(ns) || ns > 16384 || !col_ok(d[2], ncols, true) ||
+        if (kind < HX_CAT_POSITIONS || kind > HX_CAT_WEIGHTS || ns < res_lo || ns > res_hi || !col_ok(d[2], ncols, true) ||
             !col_ok(d[3], ncols, true) || !col_ok(d[4], ncols, need_v) || !col_ok(d[5], ncols, kind == HX_CAT_COMPLEX) ||
             !col_ok(d[6], ncols, false) || !maps_ok)
-            return fail(HX_ERR_ARG, "%s: bad descriptor of field %d (kind %d, nside %d; maps must be device memory)", who, f, kind, ns);
+            return fail(HX_ERR_ARG, "%s: bad descriptor of field %d (kind %d, resolution %d; maps must be device memory)", who, f, kind, ns);
         int g = 0;
         for (; g < c->ngroup; ++g)
             if (a.gnside[g] == ns && a.glon[g] == d[2] && a.glat[g] == d[3]) break;
         if (g == c->ngroup) {
-            if (g == kCatG) return fail(HX_ERR_UNSUPPORTED, "%s: more than %d (nside, lon, lat) groups", who, kCatG);
+            if (g == kCatG) return fail(HX_ERR_UNSUPPORTED, "%s: more than %d (resolution, lon, lat) groups", who, kCatG);
             a.gnside[g] = ns;
             a.glon[g] = d[2];
             a.glat[g] = d[3];
@@ -1049,6 +1137,25 @@ int page_close(CatBase *c, const PageIO &io)
     // the caller may free its columns on return: device columns are read by the kernels, pinned ones by a DMA that nothing waited for
     if (io.any_dev) HX_HIP(hipStreamSynchronize(st));
     else if (io.any_pinned) HX_HIP(hipStreamSynchronize(cs ? cs : st));
+    return HX_OK;
+}
+
+// Waits for the pages; the moments and counters of a context with one selection (counters: nan [nfield][5] at 0, nbad [ngroup] at 5 kCatF)
+int cat_moments(CatBase *c, const char *who, double *out, int64_t *bad)
+{
+    HX_TRY(ensure_ready());
+    if (!c || !out || !bad) return fail(HX_ERR_ARG, "%s: bad arguments", who);
+    hipStream_t st = rt().stream;
+    double acc[kCatF * 4];
+    unsigned long long cnt[5 * kCatF + kCatG];
+    HX_HIP(hipMemcpyAsync(acc, c->acc.p, sizeof(double) * 4 * c->nfield, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(cnt, c->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    for (int f = 0; f < c->nfield; ++f) {
+        for (int k = 0; k < 4; ++k) out[4 * f + k] = acc[4 * f + k];
+        for (int k = 0; k < 5; ++k) bad[6 * f + k] = (int64_t)cnt[5 * f + k];
+        bad[6 * f + 5] = (int64_t)cnt[5 * kCatF + c->grp[f]];
+    }
     return HX_OK;
 }
 
@@ -1164,23 +1271,7 @@ extern "C" int hx_catmap_page(hx_catmap *c, int64_t n, const double *const *cols
     return page_close(c, io);
 }
 
-extern "C" int hx_catmap_moments(hx_catmap *c, double *out, int64_t *bad)
-{
-    HX_TRY(ensure_ready());
-    if (!c || !out || !bad) return fail(HX_ERR_ARG, "hx_catmap_moments: bad arguments");
-    hipStream_t st = rt().stream;
-    double acc[kCatF * 4];
-    unsigned long long cnt[5 * kCatF + kCatG];
-    HX_HIP(hipMemcpyAsync(acc, c->acc.p, sizeof(double) * 4 * c->nfield, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(cnt, c->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    for (int f = 0; f < c->nfield; ++f) {
-        for (int k = 0; k < 4; ++k) out[4 * f + k] = acc[4 * f + k];
-        for (int k = 0; k < 5; ++k) bad[6 * f + k] = (int64_t)cnt[5 * f + k];
-        bad[6 * f + 5] = (int64_t)cnt[5 * kCatF + c->grp[f]];
-    }
-    return HX_OK;
-}
+extern "C" int hx_catmap_moments(hx_catmap *c, double *out, int64_t *bad) { return cat_moments(c, "hx_catmap_moments", out, bad); }
 
 extern "C" int hx_catmap_finish(hx_catmap *c, int field, double norm, const double *vis)
 {
@@ -1407,4 +1498,140 @@ extern "C" int hx_catmap_moments_sel(hx_catmap_sel *c, double *out, int64_t *bad
 extern "C" int hx_catmap_finish_sel(hx_catmap_sel *c, int sel, int field, double norm, const double *vis)
 {
     return cat_finish(c, "hx_catmap_finish_sel", sel, field, norm, vis);
+}
+
+// =====================================================================================
+// catalogues -> alms through the point transform (heracles.map_catalogs with a DiscreteMapper: heracles/fields.py:197-559 over
+// heracles/ducc.py:92-133)
+// =====================================================================================
+// The third context on the shared core: the field rules, the moments and the page protocol are those of hx_catmap; what a page adds to is
+// not a map but the oversampled (theta, phi) grid of the point transform (hx_nufft.hip), one per component, owned by the context and
+// resident from the first page to hx_catalm_finish.  Spreading is additive in the points, so the grid after the last page is the grid of
+// the whole catalogue, and the FFT stages and the Legendre analysis run once per field instead of once per page.  Per page and
+// (lmax, lon, lat) group: at most one tile sort, shared by every component of the group, then one spread per component.
+// The spread adds with hardware float64 atomics: alms are NOT bit-repeatable between runs (unlike the maps of hx_catmap); the moments are.
+struct hx_catalm : CatBase {
+    AlmArgs args{};
+    hx_pointsht *ps[kCatF] = {};   // borrowed: tables, sort buffers, FFT scratch and the equiangular plan of each field's band limit
+    long long n1[kCatF] = {}, nlm[kCatF] = {};
+    DevBuf grid[kCatF];            // per field: nrow grids [n1][n1]
+    DevBuf loc[kCatG];
+    ~hx_catalm() { wait(); }
+};
+
+static int catalm_init(hx_catalm *c, int64_t page_size, int ncols, int nfields, const int *desc, hx_pointsht *const *ps)
+{
+    if (page_size < 1 || page_size > 0xfffffff0ll || ncols < 2 || ncols > kCatC || nfields < 1 || nfields > kCatF || !desc || !ps)
+        return fail(HX_ERR_ARG, "hx_catalm_create: bad arguments (page_size=%lld ncols=%d nfields=%d; at most %d columns and %d fields)",
+                    (long long)page_size, ncols, nfields, kCatC, kCatF);
+    AlmArgs &a = c->args;
+    HX_TRY(cat_fields_init(c, a.c, "hx_catalm_create", page_size, ncols, nfields, desc, 1, nullptr, 0, 8191));
+    hipStream_t st = rt().stream;
+    for (int f = 0; f < nfields; ++f) {
+        int info[4];
+        if (!ps[f] || hx_pointsht_info(ps[f], info) != HX_OK || info[0] != c->nside[f])
+            return fail(HX_ERR_ARG, "hx_catalm_create: field %d needs a point transform of lmax %d", f, c->nside[f]);
+        c->ps[f] = ps[f];
+        c->n1[f] = info[2];
+        c->nlm[f] = (long long)(info[0] + 1) * (info[0] + 2) / 2;
+        HX_TRY(c->grid[f].alloc(sizeof(double) * (size_t)c->n1[f] * c->n1[f] * c->nrow[f]));
+        HX_HIP(hipMemsetAsync(c->grid[f].p, 0, c->grid[f].bytes, st));
+    }
+    for (int g = 0; g < c->ngroup; ++g) {
+        HX_TRY(c->loc[g].alloc(sizeof(double2) * page_size));
+        a.loc[g] = c->loc[g].as<double2>();
+    }
+    HX_TRY(cat_sums_init(c, nfields * 4, 5 * kCatF + kCatG));
+    a.slab = c->slab.as<double>();
+    a.nan = c->counters.as<unsigned long long>();
+    a.nbad = a.nan + 5 * kCatF;
+    return HX_OK;
+}
+
+extern "C" hx_catalm *hx_catalm_create(int64_t page_size, int ncols, int nfields, const int *desc, hx_pointsht *const *ps)
+{
+    if (ensure_ready() != HX_OK) return nullptr;
+    hx_catalm *c = new hx_catalm;
+    if (catalm_init(c, page_size, ncols, nfields, desc, ps) != HX_OK) {
+        delete c;
+        return nullptr;
+    }
+    return c;
+}
+
+extern "C" void hx_catalm_destroy(hx_catalm *c) { delete c; }
+
+extern "C" int hx_catalm_page(hx_catalm *c, int64_t n, const double *const *cols)
+{
+    HX_TRY(ensure_ready());
+    PageIO io;
+    HX_TRY(page_open(c, "hx_catalm_page", n, cols, nullptr, &io));
+    if (n == 0) return HX_OK;
+    AlmArgs a = c->args;
+    std::copy(io.col, io.col + kCatC, a.c.col);
+    hipStream_t st = rt().stream;
+    const unsigned nblocks = (unsigned)std::min<long long>((n + 255) / 256, kCatBlocks);
+    {
+        ProfScope ps("catalm_prepare");
+        switch (c->nfield) {
+#define HX_CAT_PREP(NF) case NF: hipLaunchKernelGGL(k_catalm_prepare<NF>, dim3(nblocks), dim3(256), 0, st, (long long)n, a); break;
+            HX_CAT_PREP(1) HX_CAT_PREP(2) HX_CAT_PREP(3) HX_CAT_PREP(4) HX_CAT_PREP(5) HX_CAT_PREP(6) HX_CAT_PREP(7) HX_CAT_PREP(8)
+#undef HX_CAT_PREP
+        }
+        hipLaunchKernelGGL(k_cat_reduce, dim3(1), dim3(256), 0, st, (int)nblocks, c->nfield * 4, c->slab.as<double>(), c->acc.as<double>());
+        HX_HIP(hipGetLastError());
+    }
+    // The spread kernels count the points they reject (a colatitude outside [0, pi], a non-finite value) in ps->nbad.  That counter is
+    // deliberately not read here: k_catalm_prepare wrote only valid locations, and a NaN value on a kept row is in the NaN counters,
+    // from which the caller raises.  hx_pointsht_adjoint clears the counter before its own use.
+    for (int g = 0; g < c->ngroup; ++g) {
+        ProfScope pf("catalm_spread");
+        hx_pointsht *ps = nullptr;
+        PointOrder order;
+        for (int f = 0; f < c->nfield; ++f) {
+            if (c->grp[f] != g) continue;
+            if (!ps) {  // (the fields of a group share the band limit, hence the transform: one order for all their components)
+                ps = c->ps[f];
+                HX_TRY(pointsht_order(ps, n, a.loc[g], &order));
+            }
+            for (int r = 0; r < c->nrow[f]; ++r)
+                HX_TRY(pointsht_spread_one(ps, order, n, a.loc[g], c->val[f].as<double>() + r * c->cap,
+                                           c->grid[f].as<double>() + (size_t)r * c->n1[f] * c->n1[f]));
+        }
+    }
+    return page_close(c, io);
+}
+
+extern "C" int hx_catalm_moments(hx_catalm *c, double *out, int64_t *bad) { return cat_moments(c, "hx_catalm_moments", out, bad); }
+
+extern "C" int hx_catalm_finish(hx_catalm *c, int field, int spin, double norm, const double *vis_alm, double *alm)
+{
+    HX_TRY(ensure_ready());
+    if (!c || field < 0 || field >= c->nfield || !alm) return fail(HX_ERR_ARG, "hx_catalm_finish: bad arguments");
+    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d values not supported", spin);
+    const int nrow = c->nrow[field];
+    if (spin == 2 && nrow != 2) return fail(HX_ERR_ARG, "hx_catalm_finish: a spin-2 field has two components (field %d has one)", field);
+    const long long nlm = c->nlm[field];
+    const size_t gsz = (size_t)c->n1[field] * c->n1[field];
+    InView vv;
+    OutView va;
+    HX_TRY(vv.bind(vis_alm, sizeof(double) * 2 * nlm));
+    HX_TRY(va.bind(alm, sizeof(double) * 2 * nlm * nrow));
+    {
+        ProfScope ps("catalm_finish");
+        const double *grids = c->grid[field].as<double>();
+        const GridOf resident = [&](int r, const double **grid) -> int {
+            *grid = grids + (size_t)r * gsz;
+            return HX_OK;
+        };
+        HX_TRY(pointsht_grids_to_alm(c->ps[field], spin, nrow, resident, va.as<double2>()));
+        // alm <- alm / norm - vis_alm on the real and imaginary parts: k_cat_finish over rows of 2 nlm doubles
+        const long long total = 2 * nlm * nrow;
+        const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 65536);
+        hipLaunchKernelGGL(k_cat_finish, dim3(blocks), dim3(256), 0, rt().stream, 2 * nlm, nrow, va.as<double>(), norm, vv.as<double>());
+        HX_HIP(hipGetLastError());
+    }
+    HX_TRY(va.finish());
+    HX_HIP(hipStreamSynchronize(rt().stream));  // (a staged visibility dies with this scope)
+    return HX_OK;
 }

@@ -22,6 +22,13 @@
 //   4. inverse FFT of length N: h_m(theta_j).
 // FFTs: the in-LDS power-of-two kernels of the ring stage (hx_fft_core.h); lengths above 8192 points (128 KiB) as a radix-2 / 4
 // decimation-in-frequency step over sub-transforms of 8192.
+//
+// Step 1 is additive in the points and steps 2-4 are linear, so the transform has two halves with one owner each here (declared in
+// hx_common.h): "spread n points of one component into a given grid" (pointsht_order + pointsht_spread_one: no memset) and "grids to
+// alm" (pointsht_grids_to_alm).  hx_pointsht_adjoint is memset + half one + half two on the one grid the object owns; hx_catalm
+// (hx_mapper.hip) keeps one grid per component resident over the pages of a catalogue and runs half two once at the end.
+// The spread adds with hardware float64 atomics (global, and LDS in the tile kernel), whose order is not fixed: results agree from run
+// to run to rounding, NOT bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -339,30 +346,69 @@ extern "C" int hx_pointsht_info(const hx_pointsht *ps, int *info4)
     return HX_OK;
 }
 
-extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *map,
-                                   double *alm)
+namespace hx {
+
+// ---- the two halves of the transform (hx_common.h) -------------------------------------------------------------------
+// Half one: points -> grid.  pointsht_order decides the spreading path for n points and, for the tile path, sorts them once (the order is
+// shared by every component spread from these points); pointsht_spread_one ADDS one component to a grid (no memset: a caller that
+// keeps the grid resident accumulates page after page -- spreading is additive in the points).
+int pointsht_order(hx_pointsht *ps, int64_t npoints, const double2 *loc, PointOrder *o)
 {
-    HX_TRY(ensure_ready());
-    if (!ps || !alm || (npoints > 0 && (!loc || !map))) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: null argument");
-    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d values not supported", spin);
-    if (ncomp < 1 || (spin == 2 && (ncomp & 1)) || npoints < 0) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: bad component or point count");
+    const int n1 = ps->n1, W = ps->W;
+    hipStream_t st = rt().stream;
+    // large catalogues are spread through LDS tiles (one sort per call); HX_NUFFT_TILES = 0 / 1 forces the choice
+    bool tiles = npoints >= 300000;  // measured cross-over at lmax 6144 (tools/time_pointsht.py)
+    if (const char *e = getenv("HX_NUFFT_TILES")) tiles = atoi(e) != 0;
+    if (npoints == 0 || npoints > 0xfffffff0ll) tiles = false;
+    o->tiles = tiles;
+    o->key = o->idx = nullptr;
+    if (!tiles) return HX_OK;
+    const int ntx = n1 / NUFFT_TS + 1;
+    ProfScope pf("nufft_sort");
+    HX_TRY(ps->key.alloc(sizeof(unsigned) * (size_t)npoints));
+    HX_TRY(ps->key2.alloc(sizeof(unsigned) * (size_t)npoints));
+    HX_TRY(ps->idx.alloc(sizeof(unsigned) * (size_t)npoints));
+    HX_TRY(ps->idx2.alloc(sizeof(unsigned) * (size_t)npoints));
+    const long long nblk = std::min<long long>((npoints + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(k_nufft_keys, dim3((unsigned)nblk), dim3(256), 0, st, (long long)npoints, loc, n1, W, ntx,
+                       ps->key.as<unsigned>(), ps->idx.as<unsigned>(), ps->nbad.as<unsigned long long>());
+    // all 32 bits: invalid points carry the key 0xffffffff
+    HX_TRY(rsort::radix_sort_pairs<unsigned>(ps->key.as<unsigned>(), ps->idx.as<unsigned>(), ps->key2.as<unsigned>(), ps->idx2.as<unsigned>(),
+                                             (unsigned long long)npoints, 32, ps->sort_tmp, st, &o->key, &o->idx));
+    return HX_OK;
+}
+
+int pointsht_spread_one(hx_pointsht *ps, const PointOrder &o, int64_t npoints, const double2 *loc, const double *val, double *grid)
+{
+    const int n1 = ps->n1, W = ps->W;
+    hipStream_t st = rt().stream;
+    if (o.tiles) {
+        const int ntx = n1 / NUFFT_TS + 1, nty = (n1 / 2 + W + NUFFT_TPAD) / NUFFT_TS + 1;
+        hipLaunchKernelGGL(k_nufft_spread_tiles, dim3((unsigned)(ntx * nty)), dim3(256), 0, st, (long long)npoints, loc, val, o.key, o.idx,
+                           grid, n1, W, ps->beta, ntx, ps->nbad.as<unsigned long long>());
+    } else if (npoints > 0) {
+        const long long nblk = std::min<long long>((npoints + 255) / 256, 1 << 20);
+        hipLaunchKernelGGL(k_nufft_spread, dim3((unsigned)nblk), dim3(256), 0, st, (long long)npoints, loc, val, grid, n1, W, ps->beta,
+                           ps->nbad.as<unsigned long long>());
+    }
+    HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
+// Half two: grids -> alm.  Component c's grid comes from grid_of(c) right before its three FFT stages (a caller with one grid refills it
+// there); the ring spectra of a batch then go through the Legendre analysis.  d_alm: [ncomp][nlm] on the device.
+int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &grid_of, double2 *d_alm)
+{
     hx_plan *eq = ps->eq;
     const int lmax = ps->lmax, N = ps->N, n1 = ps->n1, W = ps->W;
-    InView vloc, vmap;
-    OutView valm;
-    HX_TRY(vloc.bind(loc, sizeof(double) * 2 * (size_t)npoints));
-    HX_TRY(vmap.bind(map, sizeof(double) * (size_t)ncomp * npoints));
-    HX_TRY(valm.bind(alm, sizeof(double2) * (size_t)ncomp * eq->nlm));
     hipStream_t st = rt().stream;
     const size_t hrow = (size_t)(lmax + 1) * N;
-    HX_TRY(ps->grid.alloc(sizeof(double) * (size_t)n1 * n1));
     HX_TRY(ps->T.alloc(sizeof(double2) * (size_t)(lmax + 1) * n1));
     HX_TRY(ps->U.alloc(sizeof(double2) * hrow));
     const int maxb = analysis_max_comp(spin);
     HX_TRY(ps->h.alloc(sizeof(double2) * hrow * std::min(ncomp, maxb)));
-    HX_HIP(hipMemsetAsync(ps->nbad.p, 0, 8, st));
     NufftFft a;
-    a.src_real = ps->grid.as<double>(); a.dec = ps->dec_phi.as<double>(); a.fac = ps->fac_theta.as<double2>(); a.tw = ps->tw.as<double2>();
+    a.dec = ps->dec_phi.as<double>(); a.fac = ps->fac_theta.as<double2>(); a.tw = ps->tw.as<double2>();
     a.lmax = lmax; a.N = N; a.n1 = n1; a.twN = ps->twN;
     const int band = std::min(n1, n1 / 2 + W + 4);  // rows a point with 0 <= theta <= pi can touch
     a.row0 = (n1 - W / 2 - 2) % n1;
@@ -374,45 +420,15 @@ extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t
         else if (mode == 1) hipLaunchKernelGGL(k_nufft_fft<1>, dim3(rows), dim3(threads), lds, st, a);
         else hipLaunchKernelGGL(k_nufft_fft<2>, dim3(rows), dim3(threads), lds, st, a);
     };
-    // large catalogues are spread through LDS tiles (one sort per call); HX_NUFFT_TILES = 0 / 1 forces the choice
-    bool tiles = npoints >= 300000;  // measured cross-over at lmax 6144 (tools/time_pointsht.py)
-    if (const char *e = getenv("HX_NUFFT_TILES")) tiles = atoi(e) != 0;
-    if (npoints == 0 || npoints > 0xfffffff0ll) tiles = false;
-    const int ntx = n1 / NUFFT_TS + 1, nty = (n1 / 2 + W + NUFFT_TPAD) / NUFFT_TS + 1;
-    unsigned *skey = nullptr, *sidx = nullptr;  // the sorted (tile key, point index) pairs
-    if (tiles) {
-        ProfScope pf("nufft_sort");
-        HX_TRY(ps->key.alloc(sizeof(unsigned) * (size_t)npoints));
-        HX_TRY(ps->key2.alloc(sizeof(unsigned) * (size_t)npoints));
-        HX_TRY(ps->idx.alloc(sizeof(unsigned) * (size_t)npoints));
-        HX_TRY(ps->idx2.alloc(sizeof(unsigned) * (size_t)npoints));
-        const long long nblk = std::min<long long>((npoints + 255) / 256, 1 << 20);
-        hipLaunchKernelGGL(k_nufft_keys, dim3((unsigned)nblk), dim3(256), 0, st, (long long)npoints, vloc.as<double2>(), n1, W, ntx,
-                           ps->key.as<unsigned>(), ps->idx.as<unsigned>(), ps->nbad.as<unsigned long long>());
-        // all 32 bits: invalid points carry the key 0xffffffff
-        HX_TRY(rsort::radix_sort_pairs<unsigned>(ps->key.as<unsigned>(), ps->idx.as<unsigned>(), ps->key2.as<unsigned>(), ps->idx2.as<unsigned>(),
-                                                 (unsigned long long)npoints, 32, ps->sort_tmp, st, &skey, &sidx));
-    }
     for (int c0 = 0, nb = 0; c0 < ncomp; c0 += nb) {
         nb = analysis_next_batch(spin, ncomp - c0);
         for (int c = 0; c < nb; ++c) {
-            {
-                ProfScope pf("nufft_spread");
-                HX_HIP(hipMemsetAsync(ps->grid.p, 0, sizeof(double) * (size_t)n1 * n1, st));
-                if (tiles) {
-                    hipLaunchKernelGGL(k_nufft_spread_tiles, dim3((unsigned)(ntx * nty)), dim3(256), 0, st, (long long)npoints,
-                                       vloc.as<double2>(), vmap.as<double>() + (size_t)(c0 + c) * npoints, skey, sidx, ps->grid.as<double>(), n1, W, ps->beta, ntx,
-                                       ps->nbad.as<unsigned long long>());
-                } else if (npoints > 0) {
-                    const long long nblk = std::min<long long>((npoints + 255) / 256, 1 << 20);
-                    hipLaunchKernelGGL(k_nufft_spread, dim3((unsigned)nblk), dim3(256), 0, st, (long long)npoints, vloc.as<double2>(),
-                                       vmap.as<double>() + (size_t)(c0 + c) * npoints, ps->grid.as<double>(), n1, W, ps->beta,
-                                       ps->nbad.as<unsigned long long>());
-                }
-            }
+            const double *grid = nullptr;
+            HX_TRY(grid_of(c0 + c, &grid));
             ProfScope pf("nufft_fft");
             HX_HIP(hipMemsetAsync(ps->T.p, 0, sizeof(double2) * (size_t)(lmax + 1) * n1, st));
             HX_HIP(hipMemsetAsync(ps->U.p, 0, sizeof(double2) * hrow, st));
+            a.src_real = grid;
             a.dst = ps->T.as<double2>();
             launch(0, n1, band);
             a.src = ps->T.as<double2>(); a.dst = ps->U.as<double2>();
@@ -423,10 +439,42 @@ extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t
         }
         eq->hsrc = ps->h.as<double2>();
         eq->hsrc_stride = (long long)hrow;
-        const int rc = analysis_batch(eq, spin, nb, nullptr, valm.as<double2>() + (size_t)c0 * eq->nlm, nullptr, nullptr, nullptr, 0);
+        const int rc = analysis_batch(eq, spin, nb, nullptr, d_alm + (size_t)c0 * eq->nlm, nullptr, nullptr, nullptr, 0);
         eq->hsrc = nullptr;
         HX_TRY(rc);
     }
+    return HX_OK;
+}
+
+}  // namespace hx
+
+extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *map,
+                                   double *alm)
+{
+    HX_TRY(ensure_ready());
+    if (!ps || !alm || (npoints > 0 && (!loc || !map))) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: null argument");
+    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d values not supported", spin);
+    if (ncomp < 1 || (spin == 2 && (ncomp & 1)) || npoints < 0) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: bad component or point count");
+    const int n1 = ps->n1;
+    InView vloc, vmap;
+    OutView valm;
+    HX_TRY(vloc.bind(loc, sizeof(double) * 2 * (size_t)npoints));
+    HX_TRY(vmap.bind(map, sizeof(double) * (size_t)ncomp * npoints));
+    HX_TRY(valm.bind(alm, sizeof(double2) * (size_t)ncomp * ps->eq->nlm));
+    hipStream_t st = rt().stream;
+    HX_TRY(ps->grid.alloc(sizeof(double) * (size_t)n1 * n1));
+    HX_HIP(hipMemsetAsync(ps->nbad.p, 0, 8, st));
+    PointOrder order;
+    HX_TRY(pointsht_order(ps, npoints, vloc.as<double2>(), &order));
+    // one grid serves every component: cleared and filled right before the component's FFT stages
+    const GridOf fill = [&](int c, const double **grid) -> int {
+        ProfScope pf("nufft_spread");
+        HX_HIP(hipMemsetAsync(ps->grid.p, 0, sizeof(double) * (size_t)n1 * n1, st));
+        HX_TRY(pointsht_spread_one(ps, order, npoints, vloc.as<double2>(), vmap.as<double>() + (size_t)c * npoints, ps->grid.as<double>()));
+        *grid = ps->grid.as<double>();
+        return HX_OK;
+    };
+    HX_TRY(pointsht_grids_to_alm(ps, spin, ncomp, fill, valm.as<double2>()));
     unsigned long long nbad = 0;
     HX_HIP(hipMemcpyAsync(&nbad, ps->nbad.p, 8, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));

@@ -5,6 +5,10 @@
 stay in HBM until the last page, and the field's normalisation runs there too.  Maps, metadata, warnings and errors are those of the
 reference's fields (heracles/fields.py:197-559); see ``heracles_amd.fields``.
 
+``catalog_alms`` is the other half of the reference's ``map_catalogs``: fields whose mapper is a ``HipDiscreteMapper`` give alms, not
+maps (heracles/ducc.py:92-133).  The same page protocol feeds one ``hx_catalm`` context, whose accumulators are the oversampled grids of
+the point transform: they stay in HBM from the first page to the last, so the FFT stages and the Legendre analysis run once per field.
+
 ``transform`` is the reference's as one batched call per mapper.
 
 The reference walks ``data`` -- ``{(field name, bin): map}`` -- and transforms one map at a time (mapping.py:171).  Here the walk
@@ -25,7 +29,7 @@ import numpy as np
 
 from .core import DeviceArray, TocDict, toc_match, update_metadata
 
-__all__ = ["map_catalogs", "transform"]
+__all__ = ["map_catalogs", "catalog_alms", "transform"]
 
 
 @dataclass
@@ -124,11 +128,11 @@ def _mapped(items):
     return [it for it in items if it.kind != _VISIBILITY]
 
 
-def _kind(field):
+def _kind(field, who="map_catalogs"):
     for cls in type(field).__mro__:
         if cls.__name__ in _KINDS:
             return _KINDS[cls.__name__]
-    raise TypeError(f"map_catalogs: cannot map a field of type {type(field).__name__!r}: not one of "
+    raise TypeError(f"{who}: cannot map a field of type {type(field).__name__!r}: not one of "
                     f"{', '.join(sorted(_KINDS))}")
 
 
@@ -140,7 +144,22 @@ def _mapper_or_error(field):
 
     if not isinstance(mapper, HipHealpixMapper):
         raise NotImplementedError(f"map_catalogs: mapper of type {type(mapper).__name__!r} is not supported; catalogues are mapped "
-                                  "with HipHealpixMapper only (HipDiscreteMapper has no maps)")
+                                  "with HipHealpixMapper only (HipDiscreteMapper has no maps: catalog_alms gives its alms)")
+    return mapper
+
+
+def _discrete_mapper_or_error(field):
+    mapper = field.mapper
+    if mapper is None:
+        raise ValueError("no mapper for field")
+    from .discrete import HipDiscreteMapper
+    from .mapper import HipHealpixMapper
+
+    if isinstance(mapper, HipHealpixMapper):
+        raise NotImplementedError("catalog_alms: a HipHealpixMapper field has maps: use map_catalogs (and transform) for it")
+    if not isinstance(mapper, HipDiscreteMapper):
+        raise NotImplementedError(f"catalog_alms: mapper of type {type(mapper).__name__!r} is not supported; alms are accumulated "
+                                  "with HipDiscreteMapper only")
     return mapper
 
 
@@ -151,12 +170,12 @@ def _columns_or_error(field):
     return tuple(columns)
 
 
-def _item(key, field, catalog):
+def _item(key, field, catalog, mapper_of=_mapper_or_error, who="map_catalogs"):
     """The checks each reference field makes before its first page, in its order; raises what it raises."""
-    kind = _kind(field)
+    kind = _kind(field, who)
     if kind == _POSITIONS and field.overdensity and catalog.visibility is None:
         raise ValueError("cannot compute density contrast: no visibility in catalog")
-    item = _Item(key, field, kind, _mapper_or_error(field))
+    item = _Item(key, field, kind, mapper_of(field))
     if kind == _VISIBILITY:
         if catalog.visibility is None:
             raise ValueError("no visibility in catalog")
@@ -170,19 +189,31 @@ def _item(key, field, catalog):
     return item
 
 
-def _chunks(items, cols0=()):
-    """Split the fields of one catalogue into contexts of at most _MAX_FIELDS fields, _MAX_GROUPS (nside, lon, lat) groups and
-    _MAX_COLUMNS columns (each context reads the catalogue once); ``cols0``: columns every context reads first."""
+def _resolution(mapper):
+    """What fields must share, next to their position columns, to share a group: the nside of a HEALPix mapper, the lmax of a
+    discrete one."""
+    nside = getattr(mapper, "nside", None)
+    return mapper.lmax if nside is None else nside
+
+
+def _chunks(items, cols0=(), fits=None, who="map_catalogs"):
+    """Split the fields of one catalogue into contexts of at most _MAX_FIELDS fields, _MAX_GROUPS (nside or lmax, lon, lat) groups and
+    _MAX_COLUMNS columns (each context reads the catalogue once); ``cols0``: columns every context reads first.  ``fits(fields)``:
+    whether these fields may share a context (the memory budget of catalog_alms); it raises for a single field that cannot.
+    ``who``: the entry point named in the error."""
     chunk, groups, cols = [], set(), list(cols0)
     for it in items:
-        g = (it.mapper.nside, *it.lonlat)
+        g = (_resolution(it.mapper), *it.lonlat)
         need = lambda: [c for c in it.columns if c not in cols]
-        if chunk and (len(chunk) == _MAX_FIELDS or len(groups | {g}) > _MAX_GROUPS or len(cols) + len(need()) > _MAX_COLUMNS):
+        if chunk and (len(chunk) == _MAX_FIELDS or len(groups | {g}) > _MAX_GROUPS or len(cols) + len(need()) > _MAX_COLUMNS
+                      or (fits is not None and not fits([*chunk, it]))):
             yield chunk, cols
             chunk, groups, cols = [], set(), list(cols0)
         if len(cols) + len(need()) > _MAX_COLUMNS:
-            raise ValueError(f"map_catalogs: field {it.key[0]!r} needs {len(cols) + len(need())} columns in one context (at most "
+            raise ValueError(f"{who}: field {it.key[0]!r} needs {len(cols) + len(need())} columns in one context (at most "
                              f"{_MAX_COLUMNS})")
+        if not chunk and fits is not None:
+            fits([it])
         chunk.append(it)
         groups.add(g)
         cols.extend(need())
@@ -288,7 +319,7 @@ def _visibility_on(catalog, nside, device, message):
 _NAN_SLOTS = ("lonlat0", "lonlat1", "value", "imag", "weight")
 
 
-def _check_page_errors(items, bad):
+def _check_page_errors(items, bad, who="map_catalogs"):
     """The reference raises in page.get (NaN in a column it reads) and in hp.ang2pix (invalid positions); the first field with
     either, in field order, decides the error."""
     for f, it in enumerate(items):
@@ -297,8 +328,8 @@ def _check_page_errors(items, bad):
             if bad[f, k]:
                 raise ValueError(f'invalid values in column "{names[k]}"')
         if bad[f, 5]:
-            raise ValueError(f"map_catalogs: {int(bad[f, 5])} positions of field {it.key[0]!r} have a latitude outside [-90, 90] or a "
-                             "non-finite coordinate (healpy: THETA is out of range [0,pi])")
+            raise ValueError(f"{who}: {int(bad[f, 5])} positions of field {it.key[0]!r} have a latitude outside [-90, 90] or a "
+                             "non-finite coordinate" + (" (healpy: THETA is out of range [0,pi])" if who == "map_catalogs" else ""))
 
 
 def _normalise(it, mom, catalog):
@@ -340,7 +371,7 @@ def _result(it, tensor, catalog, extra, device_out):
     out = it.mapper.create(*shape[:-1], spin=spin)
     if isinstance(tensor, np.ndarray):
         out[...] = tensor
-    elif out.dtype == np.float64 and out.flags.c_contiguous:
+    elif out.dtype in (np.float64, np.complex128) and out.flags.c_contiguous:
         from . import _lib
 
         _lib.copy(out, tensor)
@@ -436,6 +467,183 @@ def _map_catalog(items, catalog, device, device_out):
         finally:
             ctx.close()
     return {it.key: results[it.key] for it in items}
+
+
+# ---- catalog_alms: catalogues to alms through the point transform (hx_catalm_*) --------------------------------------------------------
+
+def _nlm(lmax):
+    return (lmax + 1) * (lmax + 2) // 2
+
+
+def _point_sht(lmax):
+    """The point transform behind the fields of one band limit, at the accuracy every column is mapped with."""
+    from .discrete import get_point_sht
+
+    return get_point_sht(lmax, 1e-12)
+
+
+def _new_alm(nrow, nlm, device):
+    import torch
+
+    return torch.empty((nrow, nlm) if nrow > 1 else (nlm,), dtype=torch.complex128, device=device)
+
+
+class _CatAlm(_Context):
+    """One hx_catalm context: the fields of one pass over a catalogue, their point transforms (borrowed) and the resident grids."""
+
+    _destroy = "hx_catalm_destroy"
+
+    def __init__(self, page_size, ncols, desc, shts):
+        self._open([])
+        self.nfield, self._shts = len(shts), list(shts)
+        d = self._desc = np.ascontiguousarray(desc, dtype=np.intc).ravel()
+        ps = (C.c_void_p * len(shts))(*[s._h for s in shts])
+        self._created(self._L.hx_catalm_create(int(page_size), int(ncols), len(shts), d.ctypes.data, ps))
+
+    def page(self, n, cols):
+        self._lib.check(self._L.hx_catalm_page(self._h, int(n), self._pointers(cols)))
+
+    def moments(self):
+        mom, bad = np.empty((self.nfield, 4)), np.empty((self.nfield, 6), dtype=np.int64)
+        self._lib.check(self._L.hx_catalm_moments(self._h, mom.ctypes.data, bad.ctypes.data))
+        return mom, bad
+
+    def finish(self, f, spin, norm, vis, alm):
+        self._lib.check(self._L.hx_catalm_finish(self._h, int(f), int(spin), float(norm), self._lib.ptr(vis), self._lib.ptr(alm)))
+
+
+def _is_complex(x):
+    return x.is_complex() if hasattr(x, "data_ptr") else np.iscomplexobj(x)
+
+
+def _alm_item(key, field, catalog):
+    """_item for catalog_alms; where the field reads the visibility, it must be alms (complex), as heracles/catalog/base.py:36-44 tells
+    a visibility map from visibility alms."""
+    it = _item(key, field, catalog, _discrete_mapper_or_error, "catalog_alms")
+    if (it.kind == _VISIBILITY or (it.kind == _POSITIONS and field.overdensity)) and not _is_complex(catalog.visibility):
+        raise ValueError(f"catalog_alms: field {key[0]!r} needs the catalogue's visibility as alms (a complex array); a visibility map "
+                         "goes with map_catalogs")
+    return it
+
+
+def _visibility_alm(catalog, lmax, device, message):
+    """The catalogue's visibility alms on the device at ``lmax``; re-packed (DiscreteMapper.resample) with the reference's warning when
+    their size differs."""
+    import torch
+
+    from .discrete import alm_resample
+    from .mapper import _native
+
+    vis = catalog.visibility
+    if not hasattr(vis, "data_ptr"):
+        vis = torch.as_tensor(np.ascontiguousarray(_native(np.asarray(vis)), dtype=np.complex128))
+    vis = vis.to(device=device, dtype=torch.complex128).contiguous()
+    if vis.numel() != _nlm(lmax):
+        warnings.warn(message)
+        vis = alm_resample(vis, lmax)
+    return vis
+
+
+def _alm_visibility(items, catalog, device, device_out):
+    """{key: alm} of the ``Visibility`` items: a copy of the catalogue's visibility alms at the field's band limit."""
+    results = {}
+    for it in items:
+        if it.kind != _VISIBILITY:
+            continue
+        vis = _visibility_alm(catalog, it.mapper.lmax, device, "changing size of visibility map")
+        if catalog.visibility is vis:
+            vis = vis.clone()
+        results[it.key] = _result(it, vis, catalog, {}, device_out)
+    return results
+
+
+def _alm_fits(device):
+    """``fits`` of _chunks for catalog_alms: the grids of the fields (8 n1^2 bytes per component) within _map_budget less the scratch of
+    the finishing transforms (T, U and two components of h per band limit: 16 (lmax + 1) (n1 + 3 n1 / 2) bytes)."""
+    def fits(fields):
+        grids = sum(8 * (2 if it.kind == _COMPLEX else 1) * _point_sht(it.mapper.lmax).ngrid ** 2 for it in fields)
+        scratch = 0
+        for lmax in {it.mapper.lmax for it in fields}:
+            n1 = _point_sht(lmax).ngrid
+            scratch += 16 * (lmax + 1) * (n1 + 3 * n1 // 2)
+        budget = _map_budget(device)
+        if grids + scratch <= budget:
+            return True
+        if len(fields) == 1:
+            raise MemoryError(f"catalog_alms: field {fields[0].key[0]!r} at lmax {fields[0].mapper.lmax} needs {grids} bytes of grids "
+                              f"and {scratch} bytes of transform scratch; {budget} bytes are available")
+        return False
+
+    return fits
+
+
+def _alms_of_catalog(items, catalog, device, device_out):
+    """Alms of the ``items`` (already checked) of one catalogue; {key: alm} in the order of the items."""
+    results = _alm_visibility(items, catalog, device, device_out)
+    cap = max(1, int(catalog.page_size))
+    for chunk, cols in _chunks(_mapped(items), fits=_alm_fits(device), who="catalog_alms"):
+        index = {c: i for i, c in enumerate(cols)}
+        ix = lambda c: -1 if c is None else index[c]
+        desc = [[it.kind, it.mapper.lmax, ix(it.lonlat[0]), ix(it.lonlat[1]), ix(it.value), ix(it.imag), ix(it.weight)] for it in chunk]
+        ctx = _CatAlm(cap, len(cols), desc, [_point_sht(it.mapper.lmax) for it in chunk])
+        try:
+            for page, start, stop in _iter_pages(catalog, cap):
+                arrays = [_column(page[c], device) for c in cols]
+                if start or stop != page.size:
+                    arrays = [a[start:stop] for a in arrays]
+                ctx.page(stop - start, arrays)
+                del arrays, page
+            mom, bad = ctx.moments()
+            _check_page_errors(chunk, bad, "catalog_alms")
+            for f, it in enumerate(chunk):
+                norm, extra = _normalise(it, mom[f], catalog)
+                vis = None
+                if it.kind == _POSITIONS and it.field.overdensity:
+                    vis = _visibility_alm(catalog, it.mapper.lmax, device, "positions and visibility have different size")
+                alm = _new_alm(2 if it.kind == _COMPLEX else 1, _nlm(it.mapper.lmax), device)
+                ctx.finish(f, it.field.spin, norm, vis, alm)
+                results[it.key] = _result(it, alm, catalog, extra, device_out)
+        finally:
+            ctx.close()
+    return {it.key: results[it.key] for it in items}
+
+
+def catalog_alms(fields, catalogs, *, out=None, include=None, exclude=None, progress=None, device=None):
+    """Alms of ``fields`` for every catalogue of ``catalogs``, for fields whose mapper is a ``HipDiscreteMapper``: what the reference's
+    ``map_catalogs`` returns with a ``DiscreteMapper`` (heracles/fields.py:197-559 over heracles/ducc.py:92-133).  ``out[field name,
+    catalogue key]`` receives ``sum_p w_p v_p conj(sY_lm(lon_p, lat_p))`` over the rows the field keeps, divided by ``nbar`` /
+    ``wbar`` (``mapper.area`` is 1), less the visibility alms for ``Positions(overdensity=True)``: an array of ``mapper.create(spin=...)``,
+    or of ``mapper.create(2, spin=...)`` = (E, B) / (real, imaginary) for the two-component fields, carrying the metadata of ``create``,
+    of the catalogue and of the field.  ``out``, key order, ``include`` / ``exclude``, ``progress`` and ``device="cuda"``
+    (``DeviceArray``s around complex128 tensors) are those of ``map_catalogs``.
+
+    A catalogue's visibility, where a field reads it, is alms here (a complex numpy array or CUDA tensor).  Any object with the page
+    protocol is a catalogue; a view is read through its own iteration.  All fields of one catalogue share one pass over its pages, as
+    far as the context limits and the memory budget allow (one resident float64 grid of ``PointSHT.ngrid``^2 per component: 2.1 GB up to
+    lmax 4095, 8.6 GB above); fields that do not fit go to a further pass, and a single field that cannot fit raises ``MemoryError``.
+
+    Every column is mapped in float64 at epsilon 1e-12, whatever its dtype (the reference asks ducc0 for 1e-5 when the values are
+    float32).  The grids are filled with hardware float64 atomics: two runs agree to rounding, not bit for bit."""
+    if out is None:
+        out = TocDict()
+    total = len(fields) * len(catalogs)
+    current = 0
+    if progress is not None:
+        progress.update(current, total)
+    dev = None
+    for j, catalog in catalogs.items():
+        items = [_alm_item((i, j), field, catalog) for i, field in fields.items() if toc_match((i, j), include, exclude)]
+        if not items:
+            continue
+        if dev is None:
+            dev = _device_of(device)
+        results = _alms_of_catalog(items, catalog, dev, device is not None)
+        for key in list(results):
+            out[key] = results.pop(key)
+            current += 1
+            if progress is not None:
+                progress.update(current, total)
+    return out
 
 
 # ---- views of one base catalogue in one pass (hx_catmap_*_sel) -------------------------------------------------------------------------

@@ -352,6 +352,28 @@ int hx_catmap_moments(hx_catmap *ctx, double *out, int64_t *bad);
 int hx_catmap_finish(hx_catmap *ctx, int field, double norm, const double *vis);
 void hx_catmap_destroy(hx_catmap *ctx);
 
+/* ---- catalogues -> alms through the point transform: heracles.map_catalogs with a DiscreteMapper (heracles/ducc.py:92-133) ----------
+ * hx_catmap's field kinds, rules, moments and page protocol, with the oversampled (theta, phi) grids of hx_pointsht as the accumulators:
+ * the context owns one zeroed [n1][n1] float64 grid per component (2 for HX_CAT_COMPLEX, else 1; 8 n1^2 bytes each: 2.1 GB up to
+ * lmax 4095, 8.6 GB for lmax 4096..8191) and every page is spread into them without clearing, so the FFT stages and the Legendre
+ * analysis run once per field, in hx_catalm_finish, not once per page.  desc: 7 ints per field {kind, lmax, lon, lat, value, imag,
+ * weight}; ps[f]: the point transform of field f's lmax, BORROWED (tables, sort buffers, FFT scratch, equiangular plan) and to outlive
+ * the context.  Fields that share (lmax, lon, lat) share the points (theta, phi) = (radians(90 - lat), radians(lon mod 360)) and at most
+ * one tile sort per page (from 300000 rows; HX_NUFFT_TILES = 0 / 1 forces the choice), then one spread per component.
+ *  hx_catalm_page:    hx_catmap_page's protocol.  Rows that add nothing (kept by no field of the group, or a zero value) cost no atomics.
+ *  hx_catalm_moments: as hx_catmap_moments, the same sums in the same order (bitwise repeatable); bad[6 f + 5] counts the kept rows with a
+ *                     latitude outside [-90, 90] or a non-finite coordinate, which are never added.
+ *  hx_catalm_finish:  alm <- (grids of the field -> alm with the given spin: 0, or 2 for a two-component field: (E, B)) / norm - vis_alm,
+ *                     each operation rounded on its own (vis_alm NULL: the division only).  alm: [nrow][nlm] complex, OVERWRITTEN; vis_alm:
+ *                     [nlm] complex; host or device.  The grids are left as they were: a field can be finished again.
+ * The spread adds with hardware float64 atomics, so the alms are NOT bit-repeatable from run to run (they agree to rounding).            */
+typedef struct hx_catalm hx_catalm;
+hx_catalm *hx_catalm_create(int64_t page_size, int ncols, int nfields, const int *desc, hx_pointsht *const *ps);
+int hx_catalm_page(hx_catalm *ctx, int64_t n, const double *const *cols);
+int hx_catalm_moments(hx_catalm *ctx, double *out, int64_t *bad);
+int hx_catalm_finish(hx_catalm *ctx, int field, int spin, double norm, const double *vis_alm, double *alm);
+void hx_catalm_destroy(hx_catalm *ctx);
+
 /* ---- selections: the views of ONE base catalogue (base.where(selection)) mapped in one pass over the base's pages ------------------
  * hx_catmap_create_sel: nsel <= HX_CAT_MAX_SELECTIONS selections, the fields desc of hx_catmap_create (the same fields for every
  * selection), maps[s nfields + f] the DEVICE map of field f for selection s.  Bit s of a row's membership word is set when the base's
