@@ -10,6 +10,8 @@
 //                            counters give every key its place in the tile sorted by digit, the pairs go through LDS into that order
 //                            and leave in runs of equal digits: consecutive threads write consecutive addresses.
 // Stable (equal keys keep their input order: wave segments, rounds and lanes are all in index order), deterministic.
+// tests/csrc/sort_probe.hip calls the three routines below as the library does; tests/test_gpu_sort.py pins their keys AND values against an
+// independent stable sort at every end_bit in use, the wave / segment / tile / scan-tile edges of n and 8193 tiles (n near 2^32 is not pinned).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -201,3 +201,32 @@ def test_full_size_catalogue():
     assert pos.dtype.metadata["nbar"] == pytest.approx(nbar, rel=1e-12)
     # overdensity with unit visibility: sum(map) = sum(w) / nbar - npix = 0 up to rounding
     assert abs(fs(pos.tensor)) <= 1e-4
+
+
+@pytest.mark.parametrize("nside", [1024, 4096])  # 24 and 28 key bits with the sentinel: three full passes, four passes
+def test_one_catalogue_order_exact_at_three_and_four_sort_passes(nside):
+    """map_catalogs on device maps against the sequential loop (ordered_sum_cases.py): the page sort of hx_catmap_page, where rows of
+    weight 0 take the sentinel key npix, and k_cat_run_add.  Expected: the rows with w != 0 in catalogue order across two pages of
+    unequal size, np.add.at of w and of e * w, divided by the result's wbar with numpy's `/` (wbar itself is pinned elsewhere)."""
+    import ordered_sum_cases as osc
+    from heracles_amd.mapper import ang2pix_ring
+    from oracle import hxoracle
+
+    rng, lon, lat = osc.rows(nside + 2)
+    w = rng.choice([0.0, 0.5, 1.0, 2.0], osc.N, p=[0.1, 0.2, 0.5, 0.2])
+    e = osc.values(rng, (2, osc.N))
+    ipix = hxoracle.ang2pix_ring(nside, lon, lat)
+    np.testing.assert_array_equal(ang2pix_ring(nside, lon, lat), ipix)
+    keep = w != 0
+    upix, she = osc.reference(ipix[keep], e[:, keep] * w[keep])
+    upix_w, wht = osc.sequential(ipix[keep], w[keep])
+    np.testing.assert_array_equal(upix_w, upix)
+    cat = hx.ArrayCatalog({"lon": lon, "lat": lat, "w": w, "e1": e[0], "e2": e[1]}, page_size=120_000)
+    m = hx.HipHealpixMapper(nside, 2, deconvolve=False)
+    flds = {"WHT": hx.Weights(m, "lon", "lat", "w"), "SHE": hx.Shears(m, "lon", "lat", "e1", "e2", "w")}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        got = hx.map_catalogs(flds, {0: cat}, device="cuda")
+    for name, want in (("WHT", wht), ("SHE", she)):
+        wbar = got[name, 0].dtype.metadata["wbar"]
+        osc.check_maps(got[name, 0].tensor, upix, want / wbar, 0.0, f"{name} nside {nside}")

@@ -479,3 +479,53 @@ print("wide ok")
 """ % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HX_SORT_WIDE="1"), capture_output=True, text=True, timeout=300)
     assert res.returncode == 0 and "wide ok" in res.stdout, res.stderr[-1500:]
+
+
+# ---- ordered sums at production key widths (ordered_sum_cases.py) ------------------------------------------------------------------------
+@pytest.mark.parametrize("nside", [128, 1024, 4096])  # 18, 24 and 28 key bits: three passes with a 2-bit tail, three full passes, four passes
+def test_map_values_order_exact_at_three_and_four_sort_passes(oracle, nside):
+    """hx_map_values, ordered path, on device maps that start at 0.75: bit for bit the sequential loop at every touched pixel, every
+    other pixel untouched.  The catalogue's sums depend on their order (ordered_sum_cases.reference asserts it)."""
+    import torch
+
+    import ordered_sum_cases as osc
+    from heracles_amd.mapper import ang2pix_ring, map_values
+
+    rng, lon, lat = osc.rows(nside)
+    vals = osc.values(rng, (2, osc.N))
+    ipix = oracle.ang2pix_ring(nside, lon, lat)
+    np.testing.assert_array_equal(ang2pix_ring(nside, lon, lat), ipix)
+    upix, want = osc.reference(ipix, vals, fill=0.75)
+    maps = torch.full((2, 12 * nside**2), 0.75, dtype=torch.float64, device="cuda")
+    map_values(nside, lon, lat, maps, vals)
+    osc.check_maps(maps, upix, want, 0.75, f"nside {nside}")
+
+
+def test_map_values_order_exact_through_the_64_bit_sort_at_three_passes():
+    """The same at nside 1024 with HX_SORT_WIDE=1 (read once per process, hence the child): radix_sort_pairs<long long> over 24 key bits."""
+    import os
+    import subprocess
+    import sys
+
+    code = r"""
+import sys
+import numpy as np
+import torch
+sys.path.insert(0, %r)
+sys.path.insert(0, %r)
+import ordered_sum_cases as osc
+from oracle import hxoracle as ho
+from heracles_amd.mapper import ang2pix_ring, map_values
+nside = 1024
+rng, lon, lat = osc.rows(nside + 1)
+vals = osc.values(rng, (2, osc.N))
+ipix = ho.ang2pix_ring(nside, lon, lat)
+np.testing.assert_array_equal(ang2pix_ring(nside, lon, lat), ipix)
+upix, want = osc.reference(ipix, vals, fill=0.75)
+maps = torch.full((2, 12 * nside**2), 0.75, dtype=torch.float64, device="cuda")
+map_values(nside, lon, lat, maps, vals)
+osc.check_maps(maps, upix, want, 0.75, "wide keys")
+print("wide ok")
+""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HX_SORT_WIDE="1"), capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "wide ok" in res.stdout, res.stderr[-1500:]

@@ -96,39 +96,68 @@ def test_pixel_centres_reproduce_map2alm(spin):
     assert _err(got, np.asarray(want)) < 1e-11
 
 
-@pytest.mark.parametrize("lmax", [2100, 4200])  # FFT lengths 16384 and 32768: radix-2 / radix-4 step over in-LDS transforms
-def test_long_transforms_on_sampled_m(lmax):
-    """Away from the poles: 1e-11.  A point within a few rings of a pole puts all its weight on rings whose lambda_lm is
-    evaluated through x = cos(theta) in float64: a three-term recursion then carries l * 1.1e-16 / sin(theta) (the ring
-    is displaced by < 1e-7 arc seconds) -- the same conditioning as on the first HEALPix rings, independent of the NUFFT;
-    the oracle runs its recursion in extended precision.  Bound used: 10 * lmax * 1.1e-16 / sin(first ring)."""
-    import heracles_amd as hx
+_LONG_CASES = {}
+_LONG_STRIDE = 97
 
-    rng = np.random.default_rng(lmax)
-    n = 40
-    sht = hx.PointSHT(lmax)
-    stride = 97
 
-    def worst_error(theta, phi, v):
-        got = sht.adjoint_synthesis(np.stack([theta, phi], axis=1), v, spin=2)
-        oracle.set_mstride(stride)
+def _long_case(lmax):
+    """Points, values and the oracle's alms on every 97th m of test_long_transforms_on_sampled_m: computed once per lmax, shared by the
+    two spreading paths, never written."""
+    if lmax not in _LONG_CASES:
+        rng = np.random.default_rng(lmax)
+        n = 40
+        theta = np.arccos(rng.uniform(-0.995, 0.995, n))
+        phi = rng.uniform(0, 2 * np.pi, n)
+        v = rng.normal(size=(2, n))
+        polar = theta.copy()
+        polar[:3] = [1e-4, np.pi - 3e-4, np.pi / 2]
+        oracle.set_mstride(_LONG_STRIDE)
         try:
-            want = oracle.points2alm(theta, phi, v, lmax, spin=2)
+            wants = [oracle.points2alm(t, phi, v, lmax, spin=2) for t in (theta, polar)]
         finally:
             oracle.set_mstride(1)
+        for a in (theta, polar, phi, v, *wants):
+            a.setflags(write=False)
+        _LONG_CASES[lmax] = (phi, v, (theta, wants[0]), (polar, wants[1]))
+    return _LONG_CASES[lmax]
+
+
+def _long_transforms_on_sampled_m(lmax):
+    import heracles_amd as hx
+
+    sht = hx.PointSHT(lmax)
+    phi, v, away, polar = _long_case(lmax)
+
+    def worst_error(theta, want):
+        got = sht.adjoint_synthesis(np.stack([theta, phi], axis=1), v, spin=2)
         worst = 0.0
-        for m in range(0, lmax + 1, stride):
+        for m in range(0, lmax + 1, _LONG_STRIDE):
             lo = m * (2 * lmax + 1 - m) // 2 + m
             hi = lo + lmax - m + 1
             worst = max(worst, np.abs(got[:, lo:hi] - want[:, lo:hi]).max())
         return worst / np.abs(want).max()
 
-    theta = np.arccos(rng.uniform(-0.995, 0.995, n))
-    phi = rng.uniform(0, 2 * np.pi, n)
-    v = rng.normal(size=(2, n))
-    assert worst_error(theta, phi, v) < 1e-11
-    theta[:3] = [1e-4, np.pi - 3e-4, np.pi / 2]
-    assert worst_error(theta, phi, v) < 10 * lmax * 1.1e-16 / np.sin(np.pi / sht.nrings_circle)
+    assert worst_error(*away) < 1e-11
+    assert worst_error(*polar) < 10 * lmax * 1.1e-16 / np.sin(np.pi / sht.nrings_circle)
+
+
+@pytest.mark.parametrize("lmax", [2100, 4200])  # FFT lengths 16384 and 32768: radix-2 / radix-4 step over in-LDS transforms
+def test_long_transforms_on_sampled_m(lmax, monkeypatch):
+    """Away from the poles: 1e-11.  A point within a few rings of a pole puts all its weight on rings whose lambda_lm is
+    evaluated through x = cos(theta) in float64: a three-term recursion then carries l * 1.1e-16 / sin(theta) (the ring
+    is displaced by < 1e-7 arc seconds) -- the same conditioning as on the first HEALPix rings, independent of the NUFFT;
+    the oracle runs its recursion in extended precision.  Bound used: 10 * lmax * 1.1e-16 / sin(first ring).
+    The default spreading path (40 points: one thread per point, atomics on the grid)."""
+    monkeypatch.delenv("HX_NUFFT_TILES", raising=False)
+    _long_transforms_on_sampled_m(lmax)
+
+
+@pytest.mark.parametrize("lmax", [2100, 4200])
+def test_long_transforms_on_sampled_m_through_lds_tiles(lmax, monkeypatch):
+    """The same points, oracle result and bounds through the LDS-tile spreading (HX_NUFFT_TILES=1, read on every call): at lmax 4200
+    the (tile, point) keys of its sort take 18 bits, a third pass, and 131 841 tile blocks are launched."""
+    monkeypatch.setenv("HX_NUFFT_TILES", "1")
+    _long_transforms_on_sampled_m(lmax)
 
 
 def test_crowded_patch_many_points():

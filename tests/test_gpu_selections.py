@@ -307,3 +307,87 @@ def test_wide_keys_use_the_64_bit_sort():
         want = hx.map_catalogs(fields, {k: hx.ArrayCatalog(_rows_of(cols, keep), page_size=n)}, device="cuda")
         assert torch.equal(got["POS", k].tensor, want["POS", k].tensor), k
         del want
+
+
+# ---- ordered sums of views at production key widths (ordered_sum_cases.py) ---------------------------------------------------------------
+def _ordered_view_catalogue(nside, seed, nbins, weights):
+    import ordered_sum_cases as osc
+    from oracle import hxoracle
+
+    rng, lon, lat = osc.rows(seed)
+    cols = {"RA": lon, "DEC": lat, "W": weights(rng), "E1": osc.values(rng, osc.N), "E2": osc.values(rng, osc.N),
+            "TOM_BIN_ID": rng.integers(0, nbins, osc.N).astype(np.int64)}
+    ipix = hxoracle.ang2pix_ring(nside, lon, lat)
+    np.testing.assert_array_equal(ang2pix_ring(nside, lon, lat), ipix)
+    return cols, ipix
+
+
+def _record_passes(monkeypatch):
+    """The number of views of every hx_catmap_sel pass, as test_forced_split_equals_one_pass records them: the key width of a pass
+    depends on all its views being in it."""
+    passes = []
+    real = mp._CatMapSel
+    monkeypatch.setattr(mp, "_CatMapSel", lambda *a, **k: passes.append(a[3]) or real(*a, **k))
+    return passes
+
+
+def test_views_order_exact_at_four_sort_passes(monkeypatch):
+    """Six views at nside 1024: the keys sel * (npix + 1) + pix go up to 75 497 478, 27 bits, the narrow sort with four passes.  Every
+    view's WHT and SHE maps against the sequential loop over exactly that view's rows with w != 0, in catalogue order across two
+    pages, divided by the view's wbar with numpy's `/`."""
+    import ordered_sum_cases as osc
+
+    nside, nbins = 1024, 5
+    cols, ipix = _ordered_view_catalogue(nside, 31, nbins, lambda rng: rng.choice([0.0, 0.5, 1.0, 2.0], osc.N, p=[0.1, 0.2, 0.5, 0.2]))
+    m = hx.HipHealpixMapper(nside, 2, deconvolve=False)
+    fields = {"WHT": hx.Weights(m, "RA", "DEC", "W"), "SHE": hx.Shears(m, "RA", "DEC", "E1", "E2", "W")}
+    base = hx.ArrayCatalog(cols, page_size=120_000)
+    views = {k: base[f"TOM_BIN_ID=={k}"] for k in range(nbins)}
+    masks = {k: cols["TOM_BIN_ID"] == k for k in range(nbins)}
+    views["low"] = base["TOM_BIN_ID < 3"]  # overlaps bins 0, 1 and 2
+    masks["low"] = cols["TOM_BIN_ID"] < 3
+    passes = _record_passes(monkeypatch)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        got = hx.map_catalogs(fields, views, device="cuda")
+    assert passes == [len(views)] and set(got) == {(f, k) for k in views for f in fields}
+    for k, mask in masks.items():
+        keep = mask & (cols["W"] != 0)
+        w = cols["W"][keep]
+        upix, she = osc.reference(ipix[keep], np.array([cols["E1"][keep] * w, cols["E2"][keep] * w]))
+        _, wht = osc.sequential(ipix[keep], w)
+        for name, want in (("WHT", wht), ("SHE", she)):
+            wbar = got[name, k].dtype.metadata["wbar"]
+            osc.check_maps(got[name, k].tensor, upix, want / wbar, 0.0, f"{name} view {k}")
+
+
+def test_views_order_exact_with_64_bit_keys(monkeypatch):
+    """22 views at nside 4096: 22 (12 nside^2 + 1) > 2^32, so the (view, pixel) keys keep 64 bits through five passes.  The views overlap
+    (view k holds every row but those of bin k), so that each gives a pixel enough rows for their order to matter; the weights are
+    spread over 16 decades.  Every view against the sequential loop at its touched pixels; in all 22 maps every other pixel is 0."""
+    import torch
+
+    import ordered_sum_cases as osc
+
+    nside, nbins = 4096, 22
+    cols, ipix = _ordered_view_catalogue(nside, 37, nbins, lambda rng: osc.values(rng, osc.N))
+    cols = {k: cols[k] for k in ("RA", "DEC", "W", "TOM_BIN_ID")}
+    m = hx.HipHealpixMapper(nside, 2, deconvolve=False)
+    fields = {"WHT": hx.Weights(m, "RA", "DEC", "W")}
+    base = hx.ArrayCatalog(cols, page_size=osc.N)
+    torch.cuda.empty_cache()  # 35 GB of maps in ONE pass: what earlier tests left cached counts against the budget of a pass
+    passes = _record_passes(monkeypatch)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        got = hx.map_catalogs(fields, {k: base[f"TOM_BIN_ID!={k}"] for k in range(nbins)}, device="cuda")
+    assert passes == [nbins] and list(got) == [("WHT", k) for k in range(nbins)]
+    try:
+        for k in range(nbins):
+            keep = (cols["TOM_BIN_ID"] != k) & (cols["W"] != 0)
+            wbar = got["WHT", k].dtype.metadata["wbar"]
+            # (the input conditions are asserted for views 0, 11 and 21; the others get the same exact comparison without them)
+            upix, wht = (osc.reference if k in (0, 11, 21) else osc.sequential)(ipix[keep], cols["W"][keep])
+            osc.check_maps(got["WHT", k].tensor, upix, wht / wbar, 0.0, f"view {k}")
+    finally:
+        del got
+        torch.cuda.empty_cache()
