@@ -24,7 +24,7 @@ from .covariance import (
 )
 from .core import DeviceArray, Result, TocDict, toc_match, update_metadata
 from .discrete import HipDiscreteMapper, PointSHT, alm_resample, get_point_sht
-from .jackknife import RegionAlms, jackknife_cls, region_alms
+from .jackknife import RegionAlms, correct_footprint_naturalspice_batch, jackknife_cls, region_alms
 from .mapper import HipHealpixMapper
 from .catalog import ArrayCatalog, CatalogView, FootprintFilter, InvalidValueFilter
 from .fitscatalog import FitsCatalog
@@ -42,7 +42,7 @@ from .fields import (
 )
 from .mapping import catalog_alms, map_catalogs, transform
 from .sht import Plan, get_plan
-from .transforms import cl2corr, corr2cl, gauss_legendre, wigner_d_table
+from .transforms import cl2corr, cl2corr_columns, corr2cl, corr2cl_columns, gauss_legendre, wigner_d_table
 from .fits import read_vmap
 from .twopoint import (
     alm2cl,
@@ -59,13 +59,13 @@ from .twopoint import (
     mixmat_release,
     split_requests,
 )
-from .unmixing import naturalspice
+from .unmixing import naturalspice, naturalspice_batch
 
 __all__ = [
     "HipHealpixMapper", "HipDiscreteMapper", "PointSHT", "get_point_sht", "alm_resample", "Plan", "get_plan", "HxError", "init", "device_count", "synchronize",
     "alm2cl", "alm2cl_pairs", "alm2lmax", "angular_power_spectra", "debias_cls",
     "mixing_matrices", "mixmat", "mixmat_eb", "cl2corr", "corr2cl", "gauss_legendre",
-    "wigner_d_table", "naturalspice", "Result", "TocDict", "toc_match", "update_metadata", "DeviceArray",
+    "wigner_d_table", "naturalspice", "naturalspice_batch", "cl2corr_columns", "corr2cl_columns", "correct_footprint_naturalspice_batch", "Result", "TocDict", "toc_match", "update_metadata", "DeviceArray",
     "pinned_empty", "release_caches", "mixmat_release", "split_requests", "binned", "BinPlan", "MixmatContext", "jackknife_cls", "region_alms", "RegionAlms", "transform", "read_vmap", "apply_mixing_matrix", "invert_mixing_matrix",
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",

@@ -121,6 +121,7 @@ void mixmat_drop_cache();
 void alm2cl_drop_cache();  // hx_twopoint.hip: the buffers hx_alm2cl_pairs keeps between calls
 void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner tables hx_cl2corr / hx_corr2cl keep for the last lmax
 
+int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  // hx_transforms.hip: those tables, for hx_xi_cols.hip
 // Gauss-Legendre nodes/weights into device arrays (hx_mixmat.hip)
 int launch_gauss_legendre(int n, double *d_x, double *d_w, double *d_xlo = nullptr);  // d_xlo: node k = x[k] + xlo[k] (see k_gauss_legendre)
 

@@ -147,6 +147,18 @@ static CorrCache &corr_cache()
     return c;
 }
 
+// The cached tables of `lmax` (built if need be) for the column GEMMs of hx_xi_cols.hip: T [4][lmax + 1][kpad], weights w [lmax + 1].
+// The cache keeps its one owner here; the pointers hold until the next call with another lmax or corr_cache_drop().
+int corr_tables_view(int lmax, const double **T, const double **w, int *kpad)
+{
+    CorrCache &c = corr_cache();
+    HX_TRY(corr_tables(lmax, c));
+    *T = c.T.as<double>();
+    *w = c.w.as<double>();
+    *kpad = c.kpad;
+    return HX_OK;
+}
+
 // hx_release_caches: the nodes, weights and the four tables of the last lmax (4 (lmax + 1) kpad doubles: 1.2 GB at lmax 6144)
 void corr_cache_drop()
 {

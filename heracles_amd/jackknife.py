@@ -215,11 +215,49 @@ def correct_footprint_naturalspice(cls, cls_mm, mls0, fields, unmixed=False):
     return _pad(corr2cl(wcls), lmax)
 
 
+def correct_footprint_naturalspice_batch(cls_by_sample, cls_mm_by_sample, mls0, fields, unmixed=False, max_columns=None, ops=None):
+    """``{id: correct_footprint_naturalspice(cls_by_sample[id], cls_mm_by_sample[id], mls0, fields, unmixed)}`` with all samples in
+    one batch of columns on the matrix unit (unmixing.run_spice_plan): the data columns of every sample divide by the damped
+    alpha = xi(that sample's jackknife mask) [/ xi(full mask), shared], and come back cut at the data's band limit."""
+    from .unmixing import _band_limit, _check_samples, _dress, _pack_spectra, run_spice_plan, spice_plan
+
+    ids, first, n_data = _check_samples(cls_by_sample)
+    if list(cls_mm_by_sample) != ids:
+        raise ValueError("data and mask samples must have the same ids in the same order")
+    n_mask = _band_limit(mls0)
+    if n_data > n_mask:
+        raise ValueError("the masks' band limit is below the data's")
+    mm_first = cls_mm_by_sample[ids[0]]
+    m_spins = {k: tuple(r.spin) for k, r in mm_first.items()}
+    for i in ids:
+        mm = cls_mm_by_sample[i]
+        if list(mm) != list(mm_first) or any(_band_limit({k: r}) != n_mask or tuple(r.spin) != m_spins[k] for k, r in mm.items()):
+            raise ValueError("all mask samples must have the same keys, spins and the band limit of mls0")
+    if any(k not in mls0 or tuple(mls0[k].spin) != sp for k, sp in m_spins.items()):
+        raise KeyError("mls0 lacks a key of the jackknife mask spectra")
+    plan = spice_plan({k: tuple(r.spin) for k, r in first.items()}, m_spins, fields)
+    data = np.stack([_pack_spectra(cls_by_sample[i], n_data) for i in ids])
+    num = np.stack([_pack_spectra(cls_mm_by_sample[i], n_mask) for i in ids])
+    den = None if unmixed else _pack_spectra({k: mls0[k] for k in m_spins}, n_mask)
+    b = run_spice_plan(plan, data, num, n_mask - 1, den=den, x0=-5, num_per_sample=True, max_columns=max_columns, ops=ops)
+
+    def alpha_dtype(mm):
+        def of(mk):
+            dt = np.asarray(mm[mk].array).dtype
+            return dt if unmixed else (np.ones(1, dtype=dt) / np.ones(1, dtype=np.asarray(mls0[mk].array).dtype)).dtype
+        return of
+
+    return {i: _dress(plan, cls_by_sample[i], b[s], n_data, n_mask, alpha_dtype(cls_mm_by_sample[i])) for s, i in enumerate(ids)}
+
+
 def jackknife_cls(data_maps, vis_maps, jk_map, fields, mask_correction="Fast", unmixed=False, nd=1, progress=None,
-                  device="cuda"):
+                  device="cuda", batched=False, max_columns=None):
     """Spectra of the delete-``nd`` jackknife samples: ``{regions: {(f1, f2, i1, i2): Result}}`` as
     heracles.dices.jackknife.jackknife_cls (jackknife.py:41-90) returns them (nd = 0: ``{(): cls of the full maps}``),
-    without the FITS round trips: region alms, delete-k alms and the all-pairs sweeps stay on the device."""
+    without the FITS round trips: region alms, delete-k alms and the all-pairs sweeps stay on the device.
+
+    ``batched`` (with mask_correction "Full" only): the spectra of all samples are collected first and the footprint correction is
+    applied to them together by ``correct_footprint_naturalspice_batch``, in chunks of ``max_columns`` data columns."""
     if nd not in (0, 1, 2):
         raise ValueError("number of deletions must be 0, 1 or 2")
     if mask_correction not in ("Fast", "Full"):
@@ -233,7 +271,7 @@ def jackknife_cls(data_maps, vis_maps, jk_map, fields, mask_correction="Fast", u
         mls0 = angular_power_spectra(vis.full())
     njk = data.njk
     combos = list(combinations(range(1, njk + 1), nd))
-    out = {}
+    out, pending = {}, {}
     work = work_v = None
     import torch
 
@@ -247,10 +285,15 @@ def jackknife_cls(data_maps, vis_maps, jk_map, fields, mask_correction="Fast", u
         cls = correct_bias(cls, jk_map, *regions)
         if mask_correction == "Full":
             cls_mm = angular_power_spectra(vis.delete(regions, work_v))
-            cls = correct_footprint_naturalspice(cls, cls_mm, mls0, fields, unmixed=unmixed)
+            if batched:
+                pending[regions] = cls_mm
+            else:
+                cls = correct_footprint_naturalspice(cls, cls_mm, mls0, fields, unmixed=unmixed)
         else:
             cls = correct_footprint_fsky(cls, jk_map, *regions, unmixed=unmixed)
         out[regions] = cls
+    if pending:
+        out = correct_footprint_naturalspice_batch(out, pending, mls0, fields, unmixed=unmixed, max_columns=max_columns)
     if progress is not None:
         progress.update(len(combos), len(combos))
     return out

@@ -195,3 +195,91 @@ def corr2cl(wds):
         cl = np.array(list(cl), dtype=a.dtype)
         cls[key] = replace(wd, ell=np.arange(lmax + 1), array=cl)
     return cls
+
+
+# ---- batches of single columns on the matrix unit (hx_xi_cols.hip) -------------------------------------------------------------------
+def _is_tensor(a):
+    return hasattr(a, "data_ptr")
+
+
+def _columns_in(a, what):
+    """A (ncol, length) float64 operand: a contiguous tensor (host or device) as it is, anything else as a C-contiguous numpy array."""
+    if _is_tensor(a):
+        import torch
+
+        if a.dtype != torch.float64 or a.dim() != 2 or not a.is_contiguous():
+            raise ValueError(f"{what}: tensors must be contiguous float64 of shape (ncol, length)")
+        return a
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"{what}: expected shape (ncol, length), got {a.shape}")
+    return a
+
+
+def _columns_out(like, shape, out):
+    if out is None and _is_tensor(like):
+        import torch
+
+        return torch.empty(shape, dtype=torch.float64, device=like.device)
+    return _lib.result_array(shape, out)
+
+
+def _index(ix, ncol, what):
+    ix = np.ascontiguousarray(ix, dtype=np.int32)
+    if ix.shape != (ncol,):
+        raise ValueError(f"{what}: expected {ncol} entries, got shape {ix.shape}")
+    return ix
+
+
+def cl2corr_columns(a, families, lmax, out=None):
+    """xi[c][k] = sum_l (2l + 1) / 4 pi a[c][l] T_f[l][k] at the lmax + 1 Gauss-Legendre nodes for a batch of columns ``a`` (ncol, nl),
+    column c tied to table family ``families[c]`` (0: P_l, 1: d^l_22, 2: d^l_2-2, 3: d^l_20; l from 2 for the last three): one FP64 GEMM per
+    family against the tables ``cl2corr`` caches.  nl = a.shape[-1] <= lmax + 1 (no zero-padding needed).  numpy arrays or contiguous
+    CUDA tensors; a tensor is used in place and the result is a tensor on its device unless ``out`` says otherwise."""
+    a = _columns_in(a, "cl2corr_columns")
+    ncol, nl = a.shape
+    fam = _index(families, ncol, "families")
+    out = _columns_out(a, (ncol, int(lmax) + 1), out)
+    _lib.ensure_init()
+    _lib.check(_lib.load().hx_cl2corr_cols(int(lmax), int(nl), int(ncol), _lib.ptr(fam), _lib.ptr(a), _lib.ptr(out)))
+    return out
+
+
+def corr2cl_columns(xi, families, lmax, nl=None, out=None):
+    """b[c][l] = 2 pi sum_k w_k xi[c][k] T_f[l][k] for l < nl (default lmax + 1; 0 below l = 2 for families 1 .. 3) of a batch of
+    columns ``xi`` (ncol, lmax + 1): the way back of ``cl2corr_columns``, (ncol, nl)."""
+    xi = _columns_in(xi, "corr2cl_columns")
+    ncol = xi.shape[0]
+    if xi.shape[1] != int(lmax) + 1:
+        raise ValueError(f"corr2cl_columns: xi has {xi.shape[1]} nodes, lmax + 1 = {int(lmax) + 1}")
+    nl = int(lmax) + 1 if nl is None else int(nl)
+    fam = _index(families, ncol, "families")
+    out = _columns_out(xi, (ncol, nl), out)
+    _lib.ensure_init()
+    _lib.check(_lib.load().hx_corr2cl_cols(int(lmax), nl, int(ncol), _lib.ptr(fam), _lib.ptr(xi), _lib.ptr(out)))
+    return out
+
+
+def xi_ratio(xi_d, xi_num, num_col, ndamp, xi_den=None, den_col=None, x0=-5.0, k=50.0, out=None):
+    """out[c] = xi_d[c] / D^ndamp[c](alpha_c), alpha_c = xi_num[num_col[c]] (/ xi_den[den_col[c]] where den_col[c] >= 0),
+    D(alpha) = alpha (1 + exp(-k (log10 |alpha| - x0))): the damped mask division of ``naturalspice`` for a batch of columns, element-wise
+    in plain IEEE arithmetic (hx_xi_ratio).  ``out`` may be ``xi_d`` itself."""
+    xi_d = _columns_in(xi_d, "xi_ratio")
+    xi_num = _columns_in(xi_num, "xi_ratio")
+    ncol, n = xi_d.shape
+    num_col = _index(num_col, ncol, "num_col")
+    ndamp = _index(ndamp, ncol, "ndamp")
+    if xi_num.shape[1] != n or (num_col.size and int(num_col.max()) >= xi_num.shape[0]):
+        raise ValueError("xi_ratio: num_col points outside xi_num, or the node counts differ")
+    if xi_den is not None:
+        xi_den = _columns_in(xi_den, "xi_ratio")
+        den_col = _index(den_col, ncol, "den_col")
+        if xi_den.shape[1] != n or int(den_col.max()) >= xi_den.shape[0]:
+            raise ValueError("xi_ratio: den_col points outside xi_den, or the node counts differ")
+    else:
+        den_col = None
+    out = _columns_out(xi_d, (ncol, n), out)
+    _lib.ensure_init()
+    _lib.check(_lib.load().hx_xi_ratio(int(n), int(ncol), _lib.ptr(xi_d), _lib.ptr(xi_num), _lib.ptr(num_col), _lib.ptr(xi_den), _lib.ptr(den_col),
+                                       _lib.ptr(ndamp), float(x0), float(k), _lib.ptr(out)))
+    return out

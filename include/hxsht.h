@@ -196,7 +196,8 @@ int hx_mixmat_release(void);
  * cache of hx_mixmat / hx_mixmat_eb / hx_mixmat_batch (above; its staging buffer of a host destination also serves hx_mixctx_apply and
  * outlives hx_mixctx_destroy), the tables, partial sums and staging buffer hx_alm2cl_pairs keeps (<= 512 MB), and the Gauss-Legendre
  * nodes, weights and four Wigner tables hx_cl2corr / hx_corr2cl keep for their last lmax (4 (lmax + 1) ceil64(lmax + 1) doubles: 1.2 GB
- * at lmax 6144, 4.9 GB at 12288; naturalspice runs them at the mask's band limit).  A long-lived host
+ * at lmax 6144, 4.9 GB at 12288; naturalspice runs them at the mask's band limit; hx_cl2corr_cols / hx_corr2cl_cols read the same
+ * tables and keep nothing of their own: index lists and factors are freed before they return).  A long-lived host
  * process of the reference's loops (heracles/twopoint.py:173-299, :316-401) calls this between stages to hand the HBM back. */
 int hx_release_caches(void);
 /* ---- FITS wire format of maps and alms (heracles/io.py:128-218, "next" row) ------------------------------------
@@ -275,6 +276,25 @@ int hx_mixmat_batch(int nmask, const double *cls, int ncl, int l1max, int l2max,
  * nspec spectra at once: cls [nspec][lmax+1][4] <-> corrs [nspec][lmax+1][4].          */
 int hx_cl2corr(int lmax, int nspec, const double *cls, double *corrs);
 int hx_corr2cl(int lmax, int nspec, const double *corrs, double *cls);
+
+/* The same transforms for batches of single COLUMNS, as FP64 GEMMs on the matrix unit against those cached tables: a column is one 1-D
+ * sequence tied to one table family (0: P_l, 1: d^l_22, 2: d^l_2-2, 3: d^l_20), i.e. column 0 of hx_cl2corr with TT, column 1 with
+ * EE + BB, column 2 with EE - BB, column 3 with TE; l0 = 0 for family 0 and 2 for the others.
+ *   hx_cl2corr_cols: xi[c][k] = sum_{l0 <= l < nl} ((2l + 1) / 4 pi a[c][l]) T_f[l][k],        a [ncol][nl] -> xi [ncol][lmax+1]
+ *   hx_corr2cl_cols: b[c][l]  = 2 pi sum_k (w_k xi[c][k]) T_f[l][k] (l0 <= l < nl), 0 (l < l0), xi [ncol][lmax+1] -> b [ncol][nl]
+ * at the lmax + 1 Gauss-Legendre nodes; 1 <= nl <= lmax + 1: multipoles from nl on are not read and not written (naturalspice pads
+ * data spectra to the mask's band limit and cuts them again afterwards: nl is that cut).  family [ncol] is a host array; a, xi, b host
+ * or device.  A column's result is the same bits alone or at any position of any batch, and from run to run (no atomics, no split sums).
+ *   hx_xi_ratio: out[c][k] = xi_d[c][k] / D^ndamp[c](alpha), alpha = xi_num[num_col[c]][k], divided by xi_den[den_col[c]][k] where
+ * den_col[c] >= 0 (den_col NULL or -1: no second mask), D(alpha) = alpha (1 + exp(-k (log10 |alpha| - x0))) applied ndamp[c] times: the
+ * damped mask correlation of heracles/unmixing.py:95-101 (a mask pair two data keys look up is damped twice there: ndamp = 2 for the
+ * second) and the alpha of heracles/dices/jackknife.py:440-470, in plain IEEE arithmetic (alpha = 0: nan; vanishing alpha: 0 out).
+ * All arrays [..][n]; num_col, den_col, ndamp [ncol] host arrays (>= 0, >= -1, >= 0); xi_* and out host or device, out may be xi_d.
+ * These calls keep nothing in HBM between calls but the tables of hx_cl2corr (hx_release_caches). */
+int hx_cl2corr_cols(int lmax, int nl, int ncol, const int *family, const double *a, double *xi);
+int hx_corr2cl_cols(int lmax, int nl, int ncol, const int *family, const double *xi, double *b);
+int hx_xi_ratio(int n, int ncol, const double *xi_d, const double *xi_num, const int *num_col, const double *xi_den, const int *den_col,
+                const int *ndamp, double x0, double k, double *out);
 
 /* Replaces the m-block loop of DiscreteMapper.resample (heracles/ducc.py:145-162): re-packs m-major
  * alms from band limit lmax_in to lmax_out (truncate or zero-pad).  alm_in: [ncomp][nlm(lmax_in)]
