@@ -716,6 +716,33 @@ __global__ __launch_bounds__(256) void k_alm_reduce(PlanDev P, const LegTask *__
     }
 }
 
+// The same for the run-time-spin sweep of the vector unit (k_legendre_valu<SPIN_ANY>): rows of (E_re, E_im, B_re, B_im) per ring
+// group from l0 = max(m, s) on, summed in the fixed order of the groups; rows l < l0 of the alms are zero.
+__global__ __launch_bounds__(256) void k_alm_reduce_spin(int lmax, int s, const LegTask *__restrict__ tasks, const MTasks *__restrict__ of_m,
+                                                         const double *__restrict__ partial, long long row0, int m0, int ms,
+                                                         const double *__restrict__ fl, int add, double2 *__restrict__ alm, long long alm_stride)
+{
+    const int m = m0 + blockIdx.x * ms;
+    const int l0 = m > s ? m : s;
+    const MTasks mt = of_m[m];
+    const int nl = lmax - m + 1;
+    for (int i = threadIdx.x; i < nl * 2; i += blockDim.x) {
+        const int l = m + (i >> 1), c = i & 1;
+        double2 v = make_double2(0.0, 0.0);
+        if (l >= l0) {
+            for (int t = 0; t < mt.count; ++t) {
+                const double *p = partial + (tasks[mt.first + t].pout - row0 + (l - l0)) * 4 + 2 * c;
+                v.x += p[0];
+                v.y += p[1];
+            }
+            if (fl) { v.x *= fl[l]; v.y *= fl[l]; }
+        }
+        double2 *dst = alm + (long long)c * alm_stride + almidx(lmax, l, m);
+        if (add) { const double2 o = *dst; v.x += o.x; v.y += o.y; }
+        *dst = v;
+    }
+}
+
 // =====================================================================================
 // host side: task list, m-chunking, launch sequence
 // =====================================================================================
@@ -760,6 +787,12 @@ static SweepShape sweep_shape(int spin, int nb)
     else sh.nbx = (rem + 3) / 4;
     sh.ncol = NCOL * sh.ng + 4 * sh.nbx;
     return sh;
+}
+bool analysis_generic_spin(int spin)
+{
+    if (spin != 2) return spin != 0;
+    const char *e = getenv("HX_SPIN_GENERIC");  // test hook: spin 2 through the run-time-spin sweep as well
+    return e && atoi(e) != 0;
 }
 int analysis_max_comp(int spin) { return spin == 2 ? 8 * NGMAX + 4 : 8 * NGMAX; }
 
@@ -825,7 +858,7 @@ static int build_task_set(hx_plan *pl, int spin, int nw, hx_plan::TaskSet &ts)
     for (int m = 0; m <= lmax; ++m) {
         ts.rows_before_m[m] = rows;
         ts.arow[m] = arows;
-        const int l0 = spin == 0 ? m : std::max(m, 2);
+        const int l0 = std::max(m, spin);
         if (l0 <= lmax) arows += (long long)LBLK * ((lmax - l0) / LBLK + 1);
         ts.of_m[m].first = (int)ts.tasks.size();
         if (l0 <= lmax) {
@@ -918,8 +951,15 @@ static int launch_chunk(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int n
 // The ring Fourier stage runs once for the whole batch.
 static bool valu_batch(int spin, int nb) { return sweep_shape(spin, nb).valu != 0; }
 
-int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **out, int blocks)
+int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **out, int blocks, bool generic)
 {
+    if (generic) {  // tables and tasks of this spin weight: never those of spin 2
+        hx_plan::SpinSet *set = nullptr;
+        HX_TRY(ensure_rec_s(pl, spin, &set));
+        HX_TRY(build_task_set(pl, spin, valu_task_blocks(spin), set->ts));
+        *out = &set->ts;
+        return HX_OK;
+    }
     if (spin) HX_TRY(ensure_rec2(pl));
     if (blocks <= 0) blocks = valu_task_blocks(spin);
     if (blocks != valu_task_blocks(spin) && blocks != 8) return fail(HX_ERR_ARG, "valu_tasks: %d ring blocks per task", blocks);
@@ -951,10 +991,10 @@ int synth_duo_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **out)
 }
 
 static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
-                               const double *d_pw, const double *d_fl, int add)
+                               const double *d_pw, const double *d_fl, int add, bool generic = false)
 {
     hx_plan::TaskSet *tsp = nullptr;
-    HX_TRY(valu_tasks(pl, spin, &tsp));
+    HX_TRY(valu_tasks(pl, spin, &tsp, 0, generic));
     hx_plan::TaskSet &ts = *tsp;
     if (pl->hsrc == nullptr && pl->nssrc == nullptr) {
         HX_TRY(pl->Y.alloc(sizeof(double2) * (size_t)pl->ny * nb));
@@ -994,9 +1034,12 @@ static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_ma
     for (int c0 = 0; c0 < nb; c0 += unit)
         for (auto &ch : chunks) {
             const int m0 = ch.first, m1 = ch.second, nm = (m1 - m0 + ms - 1) / ms;
-            HX_TRY(launch_valu_chunk(pl, spin, ts, m0, m1, c0, d_rw));
+            HX_TRY(launch_valu_chunk(pl, spin, ts, m0, m1, c0, d_rw, generic));
             ProfScope ps("alm_reduce");
-            if (spin == 0)
+            if (generic)
+                hipLaunchKernelGGL(k_alm_reduce_spin, dim3(nm), dim3(256), 0, rt().stream, lmax, spin, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
+                                   pl->partial.as<double>(), ts.rows_before_m[m0], m0, ms, d_fl, add, d_alms + (size_t)c0 * pl->nlm, pl->nlm);
+            else if (spin == 0)
                 hipLaunchKernelGGL(k_alm_reduce<0>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
                                    pl->partial.as<double>(), ts.rows_before_m[m0], m0, ms, 1, 1, pcol, d_fl, add, d_alms + (size_t)c0 * pl->nlm, pl->nlm, nullptr, nullptr);
             else
@@ -1013,6 +1056,16 @@ static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_ma
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
                    const double *d_pw, const double *d_fl, int add)
 {
+    if (pl->hsrc ? analysis_generic_spin(spin) : (spin != 0 && spin != 2)) {
+        // one (Q, U) field per sweep of the run-time-spin kernel; the rings of the point transform only
+        if (!pl->hsrc) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
+        if (spin < 0 || nb < 2 || (nb & 1)) return fail(HX_ERR_ARG, "analysis_batch: %d components of spin %d", nb, spin);
+        if (spin > pl->lmax) {  // no l >= s below the band limit
+            if (!add) HX_HIP(hipMemsetAsync(d_alms, 0, sizeof(double2) * (size_t)pl->nlm * nb, rt().stream));
+            return HX_OK;
+        }
+        return analysis_batch_valu(pl, spin, nb, d_maps, d_alms, d_rw, d_pw, d_fl, add, true);
+    }
     if (valu_batch(spin, nb)) return analysis_batch_valu(pl, spin, nb, d_maps, d_alms, d_rw, d_pw, d_fl, add);
     const int sidx = spin ? 1 : 0;
     HX_TRY(build_tasks(pl, spin));

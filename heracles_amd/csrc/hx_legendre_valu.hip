@@ -1,4 +1,6 @@
 // hx_legendre_valu.hip -- Legendre / Wigner-d analysis of ONE map (spin 0) or ONE (Q,U) field (spin 2) on the FP64 vector unit.
+// A field of any other spin weight s >= 1 (point transform only) runs through the spin-2 code with s, its seeds and its tables
+// given at run time: the template value SPIN_ANY.
 //
 // The call the reference itself makes is a single-map transform (heracles/mapping.py:171 -> heracles/healpy.py:183-189: one
 // hp.map2alm per (field, bin)).  With two (spin 0) or four (spin 2) real columns there is nothing for a matrix instruction to
@@ -51,6 +53,8 @@ __device__ unsigned long long g_valu_flops;
 struct ValuParams {
     PlanDev P;
     const LegTask *__restrict__ tasks;  // tasks [t0, t1) of the m-chunk
+    const double *__restrict__ kfs;     // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinSet::kf)
+    int s;
     const double *__restrict__ F;       // [(m - m0) / ms][rp][NF]
     double *__restrict__ partial;       // [row - row0][NA]
     int m0, ms;                         // the chunk holds the orders m0 + k ms (tasks of other orders in the list return at once)
@@ -63,12 +67,14 @@ struct ValuParams {
 //   spin 2: (U, V, U', V') complex with U = P+_N, V = P-_S, U' = P-_N, V' = P+_S, P+- = -(Q +- iU)/2:
 //           with G = sum_rings lambda+ U +- lambda- V', K = sum_rings lambda- U' +- lambda+ V  (+ for l + m even, - for odd)
 //           E = G + K, B = -i (G - K)  (the columns B+(P) = [Pr, Pi, Pi, -Pr], B-(P) = [Pr, Pi, -Pi, Pr] of k_fourier_combine)
+//   spin s (SPIN_ANY): as spin 2 with P+- of weight +-s; E = G + (-1)^s K, B = -i (G - (-1)^s K): for an odd s the operands of K
+//           (U' and V) are stored with the opposite sign, and everything downstream is the spin-2 code
 // grid: x = m - m0, y = blocks of 256 ring pairs; one thread per ring pair.
 // =====================================================================================
 template <int SPIN>
 __global__ __launch_bounds__(256) void k_fourier_combine_valu(PlanDev P, const double2 *__restrict__ Y, int c0, int m0, int ms,
                                                               const double *__restrict__ rw, const LegTask *__restrict__ tasks,
-                                                              const MTasks *__restrict__ of_m, double *__restrict__ F)
+                                                              const MTasks *__restrict__ of_m, double *__restrict__ F, int s)
 {
     constexpr int NF = ValuCfg<SPIN>::NF;
     const int m = m0 + blockIdx.x * ms;
@@ -89,10 +95,11 @@ __global__ __launch_bounds__(256) void k_fourier_combine_valu(PlanDev P, const d
             o[2] = fn.x - fs.x; o[3] = fn.y - fs.y;
         } else {
             double2 qn, qs, un, us;
-            ring_modes_ns(P, Y, c0, rp, m, ram, qn, qs);
-            ring_modes_ns(P, Y, c0 + 1, rp, m, ram, un, us);
-            const double2 ppn = cscale(cadd(qn, mul_pi(un)), -0.5), pmn = cscale(csub(qn, mul_pi(un)), -0.5);
-            const double2 pps = cscale(cadd(qs, mul_pi(us)), -0.5), pms = cscale(csub(qs, mul_pi(us)), -0.5);
+            ring_modes_ns(P, Y, c0, rp, m, ram, qn, qs, SPIN == SPIN_ANY ? s : 0);
+            ring_modes_ns(P, Y, c0 + 1, rp, m, ram, un, us, SPIN == SPIN_ANY ? s : 0);
+            const double ks = (SPIN == SPIN_ANY && (s & 1)) ? 0.5 : -0.5;  // the sign of K's operands
+            const double2 ppn = cscale(cadd(qn, mul_pi(un)), -0.5), pmn = cscale(csub(qn, mul_pi(un)), ks);
+            const double2 pps = cscale(cadd(qs, mul_pi(us)), -0.5), pms = cscale(csub(qs, mul_pi(us)), ks);
             o[0] = ppn.x; o[1] = ppn.y; o[2] = pms.x; o[3] = pms.y;
             o[4] = pmn.x; o[5] = pmn.y; o[6] = pps.x; o[7] = pps.y;
         }
@@ -190,8 +197,8 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
     const LegTask task = A.tasks[blockIdx.x];
     const int m = task.m, lmax = P.lmax, lane = threadIdx.x;
     if ((m - A.m0) % A.ms) return;       // an order of another rank (m-sharded route: every ms-th order is ours)
-    const int l0 = SPIN == 0 ? m : (m > 2 ? m : 2);
-    const int off = (l0 + m) & 1;        // parity of l + m at the first l (spin 2, m = 1 only)
+    const int l0 = SPIN == 0 ? m : (SPIN == 2 ? (m > 2 ? m : 2) : (m > A.s ? m : A.s));
+    const int off = (l0 + m) & 1;        // parity of l + m at the first l (spin 2: m = 1 only; spin s: m < s)
     const long long cb = almidx(lmax, 0, m);
     const int coff = SPIN == 0 ? 0 : 1;  // spin-2 coefficients are indexed by the target l
 
@@ -223,7 +230,8 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
                 vc[r][1] = b.v; sc[r][1] = b.e;
             } else {
                 SVal sp, sm;
-                spin2_seeds(m, P.sth[rp], P.omz[rp], P.kfac2[m], sp, sm);
+                if (SPIN == 2) spin2_seeds(m, P.sth[rp], P.omz[rp], P.kfac2[m], sp, sm);
+                else spin_seeds(A.s, m, P.sth[rp], P.omz[rp], A.kfs[m], sp, sm);
                 vc[r][0] = sp.v; sc[r][0] = sp.e;
                 vc[r][1] = sm.v; sc[r][1] = sm.e;
             }
@@ -374,7 +382,7 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
                     // spin 0: (s, d) belong to chains 0, 1; spin 2: lambda+ (chain 0) multiplies U and V, lambda- (chain 1) U' and V'
                     const bool lv = sc[r][(SPIN == 0 ? q >= 2 : q >= 4) ? 1 : 0] == 0;
                     const double2 t = *reinterpret_cast<const double2 *>(fp + q);
-                    const bool neg = SPIN == 2 && off && (q & 2);  // V, V': the alternating sign starts with -
+                    const bool neg = SPIN != 0 && off && (q & 2);  // V, V': the alternating sign starts with -
                     f[r][q] = lv ? (neg ? -t.x : t.x) : 0.0;
                     f[r][q + 1] = lv ? (neg ? -t.y : t.y) : 0.0;
                 }
@@ -397,7 +405,7 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
         const int idx = lane >> SH, s = idx / NA, a = idx % NA;
         double out = acc[0] * als[buf][sb * LB + s];
         int col = a;
-        if (SPIN == 2) {
+        if (SPIN != 0) {
             // lanes of accumulator a and a ^ 2 (G <-> K) differ in lane bit SH + 1: E = G + K, B = -i (G - K)
             const double oth = __shfl_xor(out, 2 << SH);
             // a = 0: G_re -> E_re = G_re + K_re (col 0); a = 1: G_im -> E_im (col 1); a = 2: K_re -> B_im = K_re - G_re (col 3);
@@ -753,7 +761,7 @@ int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, co
 // host: one m-chunk of one map / field
 // =====================================================================================
 template <int SPIN>
-static int launch_valu_chunk_t(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw)
+static int launch_valu_chunk_t(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, int s)
 {
     hipStream_t st = rt().stream;
     PlanDev P = pl->dev();
@@ -764,17 +772,23 @@ static int launch_valu_chunk_t(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1
         ProfScope ps("fourier_combine");
         dim3 grid((m1 - m0 + ms - 1) / ms, (pl->nrp_pad + 255) / 256);
         hipLaunchKernelGGL(k_fourier_combine_valu<SPIN>, grid, dim3(256), 0, st, P, pl->Y.as<double2>(), c0, m0, ms, d_rw,
-                           ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->F.as<double>());
+                           ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->F.as<double>(), s);
     }
     if (t1 > t0) {
         ProfScope ps("legendre_analysis");
-        ProfScope ps2(SPIN == 0 ? "legendre_analysis_s0" : "legendre_analysis_s2");
+        ProfScope ps2(SPIN == 0 ? "legendre_analysis_s0" : (SPIN == 2 ? "legendre_analysis_s2" : "legendre_analysis_spin"));
         ProfScope ps3("legendre_valu");
         ValuParams A;
         A.P = P; A.tasks = ts.d_tasks.as<LegTask>() + t0; A.F = pl->F.as<double>(); A.partial = pl->partial.as<double>();
         A.m0 = m0; A.ms = ms; A.row0 = ts.rows_before_m[m0];
+        A.kfs = nullptr; A.s = s;
         const double2 *cn = SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
         const double *al = SPIN == 0 ? pl->al0.as<double>() : pl->al2.as<double>();
+        if (SPIN == SPIN_ANY) {
+            hx_plan::SpinSet *set = nullptr;
+            HX_TRY(ensure_rec_s(pl, s, &set));
+            A.kfs = set->kf.as<double>(); cn = set->cn.as<double2>(); al = set->al.as<double>();
+        }
         hipLaunchKernelGGL(k_legendre_valu<SPIN>, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, A, cn, al);
     }
     HX_HIP(hipGetLastError());
@@ -789,9 +803,10 @@ int valu_exec_flops(unsigned long long *v, bool reset)
     return HX_OK;
 }
 
-int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw)
+int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic)
 {
-    return spin == 0 ? launch_valu_chunk_t<0>(pl, ts, m0, m1, c0, d_rw) : launch_valu_chunk_t<2>(pl, ts, m0, m1, c0, d_rw);
+    if (generic) return launch_valu_chunk_t<SPIN_ANY>(pl, ts, m0, m1, c0, d_rw, spin);
+    return spin == 0 ? launch_valu_chunk_t<0>(pl, ts, m0, m1, c0, d_rw, 0) : launch_valu_chunk_t<2>(pl, ts, m0, m1, c0, d_rw, 2);
 }
 
 }  // namespace hx

@@ -1608,9 +1608,9 @@ extern "C" int hx_catalm_finish(hx_catalm *c, int field, int spin, double norm, 
 {
     HX_TRY(ensure_ready());
     if (!c || field < 0 || field >= c->nfield || !alm) return fail(HX_ERR_ARG, "hx_catalm_finish: bad arguments");
-    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d values not supported", spin);
+    if (spin < 0) return fail(HX_ERR_ARG, "hx_catalm_finish: negative spin weight %d", spin);
     const int nrow = c->nrow[field];
-    if (spin == 2 && nrow != 2) return fail(HX_ERR_ARG, "hx_catalm_finish: a spin-2 field has two components (field %d has one)", field);
+    if (spin > 0 && nrow != 2) return fail(HX_ERR_ARG, "hx_catalm_finish: a spin-%d field has two components (field %d has one)", spin, field);
     const long long nlm = c->nlm[field];
     const size_t gsz = (size_t)c->n1[field] * c->n1[field];
     InView vv;

@@ -405,7 +405,8 @@ int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &gr
     const size_t hrow = (size_t)(lmax + 1) * N;
     HX_TRY(ps->T.alloc(sizeof(double2) * (size_t)(lmax + 1) * n1));
     HX_TRY(ps->U.alloc(sizeof(double2) * hrow));
-    const int maxb = analysis_max_comp(spin);
+    const bool generic = analysis_generic_spin(spin);  // a spin weight other than 0 and 2: one field per Legendre sweep
+    const int maxb = generic ? 2 : analysis_max_comp(spin);
     HX_TRY(ps->h.alloc(sizeof(double2) * hrow * std::min(ncomp, maxb)));
     NufftFft a;
     a.dec = ps->dec_phi.as<double>(); a.fac = ps->fac_theta.as<double2>(); a.tw = ps->tw.as<double2>();
@@ -421,7 +422,8 @@ int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &gr
         else hipLaunchKernelGGL(k_nufft_fft<2>, dim3(rows), dim3(threads), lds, st, a);
     };
     for (int c0 = 0, nb = 0; c0 < ncomp; c0 += nb) {
-        nb = analysis_next_batch(spin, ncomp - c0);
+        nb = generic ? std::min(2, ncomp - c0) : analysis_next_batch(spin, ncomp - c0);
+        if (nb <= 0) return fail(HX_ERR_ARG, "point transform: %d components of spin %d", ncomp, spin);
         for (int c = 0; c < nb; ++c) {
             const double *grid = nullptr;
             HX_TRY(grid_of(c0 + c, &grid));
@@ -453,8 +455,8 @@ extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t
 {
     HX_TRY(ensure_ready());
     if (!ps || !alm || (npoints > 0 && (!loc || !map))) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: null argument");
-    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d values not supported", spin);
-    if (ncomp < 1 || (spin == 2 && (ncomp & 1)) || npoints < 0) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: bad component or point count");
+    if (spin < 0) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: negative spin weight %d", spin);
+    if (ncomp < 1 || (spin > 0 && (ncomp & 1)) || npoints < 0) return fail(HX_ERR_ARG, "hx_pointsht_adjoint: bad component or point count");
     const int n1 = ps->n1;
     InView vloc, vmap;
     OutView valm;

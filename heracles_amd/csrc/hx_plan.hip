@@ -71,6 +71,35 @@ __global__ void k_init_norm2(int lmax, double2 *__restrict__ coef, double *__res
         a0 = a1;
     }
 }
+
+// k_init_norm2 for a spin weight s >= 1: the same one-step recursion with n = -s in place of -2, from l0 = max(m, s).  The (+s)
+// chain runs with (p', +q'), the (-s) chain with (p', -q'): one table serves both.
+__global__ void k_init_norm_s(int lmax, int s, double2 *__restrict__ coef, double *__restrict__ alpha)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > lmax) return;
+    const int l0 = m > s ? m : s;
+    double am1 = 1.0, a0 = 1.0;  // alpha_{l-1}, alpha_l
+    for (int l = l0; l <= lmax; ++l) {
+        alpha[almidx(lmax, l, m)] = a0;
+        if (l == lmax) break;
+        // coefficients of the step l -> l+1 (n = -s)
+        const double k = l, lp = l + 1.0, dm = m, dn = -(double)s;
+        const double den = k * sqrt((lp * lp - dm * dm) * (lp * lp - dn * dn));
+        const double r1 = sqrt((2.0 * k + 3.0) / (2.0 * k + 1.0));
+        const double p = r1 * (2.0 * k + 1.0) * k * lp / den;
+        const double q = -r1 * (2.0 * k + 1.0) * dm * dn / den;
+        double a1 = 1.0;
+        if (l > l0) {
+            const double r2 = sqrt((2.0 * k + 3.0) / (2.0 * k - 1.0));
+            const double r = r2 * lp * sqrt((k * k - dm * dm) * (k * k - dn * dn)) / den;
+            a1 = r * am1;
+        }
+        coef[almidx(lmax, l + 1, m)] = make_double2(p * a0 / a1, q * a0 / a1);
+        am1 = a0;
+        a0 = a1;
+    }
+}
 }  // namespace hx
 
 using namespace hx;
@@ -248,8 +277,10 @@ extern "C" int hx_plan_release_scratch(hx_plan *pl)
 extern "C" int64_t hx_plan_scratch_bytes(const hx_plan *pl)
 {
     if (!pl) return 0;
+    size_t spin_tables = 0;
+    for (const auto &kv : pl->spin_sets) spin_tables += kv.second.cn.bytes + kv.second.al.bytes;
     return (int64_t)(pl->stage[0].bytes + pl->stage[1].bytes + pl->stage[2].bytes + pl->resid_maps.bytes + pl->Y.bytes + pl->F.bytes + pl->partial.bytes + pl->rec0.bytes + pl->rec2.bytes + pl->cn0.bytes + pl->al0.bytes + pl->cn2.bytes + pl->al2.bytes +
-                     pl->bhat.bytes + pl->syn_tab.bytes);
+                     pl->bhat.bytes + pl->syn_tab.bytes + spin_tables);
 }
 
 extern "C" int hx_plan_last_chunks(const hx_plan *pl) { return pl ? pl->last_chunks : 0; }
@@ -263,6 +294,42 @@ int ensure_rec2(hx_plan *pl)
     HX_HIP(hipMemsetAsync(pl->cn2.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), rt().stream));
     HX_HIP(hipMemsetAsync(pl->al2.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), rt().stream));
     hipLaunchKernelGGL(k_init_norm2, dim3((pl->lmax + 64) / 64), dim3(64), 0, rt().stream, pl->lmax, pl->cn2.as<double2>(), pl->al2.as<double>());
+    HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
+int ensure_rec_s(hx_plan *pl, int s, hx_plan::SpinSet **out)
+{
+    const int lmax = pl->lmax;
+    if (s < 1 || s > lmax) return fail(HX_ERR_ARG, "ensure_rec_s: spin %d at lmax %d", s, lmax);
+    hx_plan::SpinSet &set = pl->spin_sets[s];
+    *out = &set;
+    if (set.cn.p && set.al.p && set.kf.p) return HX_OK;
+    // seed factors of spin_seeds, by incremental products like kfac2 (upwards and downwards from m = s, where the factorial ratio is 1):
+    //   m >= s: (-1)^m sqrt((2m+1)/4pi) sqrt((2m)!/((m+s)!(m-s)!)) 2^-(m-s);   m < s: sqrt((2s+1)/4pi) sqrt((2s)!/((s+m)!(s-m)!)) 2^-(s-m)
+    std::vector<double> kf(lmax + 1);
+    {
+        const long double fourpi = 4.0L * 3.141592653589793238462643383279502884L;
+        long double k = 1.0L;
+        for (int m = s; m <= lmax; ++m) {
+            if (m > s) k *= sqrtl((2.0L * m) * (2.0L * m - 1.0L) / ((long double)(m - s) * (m + s))) / 2.0L;
+            const long double v = k * sqrtl((2.0L * m + 1.0L) / fourpi);
+            kf[m] = (double)((m & 1) ? -v : v);
+        }
+        k = sqrtl((2.0L * s + 1.0L) / fourpi);
+        for (int m = s - 1; m >= 0; --m) {
+            k *= sqrtl((long double)(s + m + 1) / (s - m)) / 2.0L;
+            kf[m] = (double)k;
+        }
+    }
+    for (double v : kf)
+        if (!std::isfinite(v)) return fail(HX_ERR_UNSUPPORTED, "spin-%d values: the seeds of the recursion leave the range of a double", s);
+    HX_TRY(upload(set.kf, kf));
+    HX_TRY(set.cn.alloc(sizeof(double2) * (pl->nlm + TABLE_PAD)));
+    HX_TRY(set.al.alloc(sizeof(double) * (pl->nlm + TABLE_PAD)));
+    HX_HIP(hipMemsetAsync(set.cn.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), rt().stream));
+    HX_HIP(hipMemsetAsync(set.al.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), rt().stream));
+    hipLaunchKernelGGL(k_init_norm_s, dim3((lmax + 64) / 64), dim3(64), 0, rt().stream, lmax, s, set.cn.as<double2>(), set.al.as<double>());
     HX_HIP(hipGetLastError());
     return HX_OK;
 }

@@ -41,6 +41,7 @@ constexpr int TABLE_PAD = 512;
 constexpr int NGMAX = 2;   // column groups per analysis launch
 constexpr int RBLK = 32;   // ring pairs per wave of the Legendre analysis kernel
 constexpr double SC_BIG = 0x1p+300, SC_SMALL = 0x1p-300;
+constexpr int SPIN_ANY = -1;  // template value of the vector-unit analysis kernels for a spin weight s >= 1 given at run time
 
 struct LegTask {
     int m;
@@ -174,6 +175,29 @@ __device__ inline void spin2_seeds(int m, double sth, double omx, double kfac2m,
     snorm_small(sm);
 }
 
+// seeds of the recursions of a spin weight s >= 1 at l0 = max(m, s): sp = (+s)lambda_{l0 m}, sm = (-s)lambda_{l0 m}.  With
+// sh = sin(theta/2), ch = cos(theta/2), N_l = sqrt((2l+1)/4pi):
+//   m >= s:  (-1)^m N_m sqrt((2m)!/((m+s)!(m-s)!)) (sh ch)^(m-s)  x  sh^(2s) (+s) / ch^(2s) (-s)
+//   m <  s:  N_s sqrt((2s)!/((s+m)!(s-m)!)) (sh ch)^(s-m)  x  (-1)^m sh^(2m) (+s) / (-1)^s ch^(2m) (-s)
+// kfsm = the factor in front of the powers x 2^-|m-s| (sh ch = sin(theta) / 2), for m >= s with its sign: hx_plan::SpinSet::kf.
+// At s = 2 these are spin2_seeds.
+__device__ inline void spin_seeds(int s, int m, double sth, double omx, double kfsm, SVal &sp, SVal &sm)
+{
+    const double opx = 2.0 - omx;
+    SVal b = spow(sth, m >= s ? m - s : s - m);
+    b.v *= kfsm;
+    const int n = m >= s ? s : m;
+    const SVal ps = spow(0.5 * omx, n), pc = spow(0.5 * opx, n);
+    sp.v = b.v * ps.v; sp.e = b.e + ps.e;
+    sm.v = b.v * pc.v; sm.e = b.e + pc.e;
+    if (m < s) {
+        if (m & 1) sp.v = -sp.v;
+        if (s & 1) sm.v = -sm.v;
+    }
+    snorm_small(sp);
+    snorm_small(sm);
+}
+
 #ifdef __HIPCC__
 using namespace hxfft;
 // What a ring pair needs at one m, whatever the component: where Z[m] and Z[-m] sit in its spectrum (X[4k+r] = Y_r[k]) and
@@ -186,9 +210,10 @@ struct RingAtM {
     int hasS;
 };
 
-// F_N(m), F_S(m) of ring pair rp for component c, including phase and quadrature weight
+// F_N(m), F_S(m) of ring pair rp for component c, including phase and quadrature weight; s = spin weight of the field the
+// component belongs to (its parity matters on the equiangular rings only)
 __device__ inline void ring_modes_ns(const PlanDev &P, const double2 *__restrict__ Y, int c, int rp, int m,
-                                     const RingAtM &r, double2 &FN, double2 &FS)
+                                     const RingAtM &r, double2 &FN, double2 &FS, int s = 0)
 {
     if (P.nssrc) {
         const double4 v = P.nssrc[c][(long long)((m - P.ns_m0) / P.ns_ms) * P.nrp_pad + rp];
@@ -198,10 +223,10 @@ __device__ inline void ring_modes_ns(const PlanDev &P, const double2 *__restrict
     }
     if (P.hsrc) {
         // equiangular rings theta_j = 2 pi (j + 1/2) / N of the point transform: the spectrum h_m is given on the full circle,
-        // lambda_lm(2 pi - theta) = (-1)^m lambda_lm(theta) (both spins) folds the second half onto the rings
+        // (+-s)lambda_lm(2 pi - theta) = (-1)^(m + s) (+-s)lambda_lm(theta) folds the second half onto the rings
         const double w = r.ph.x;
         const double2 *h = P.hsrc + (long long)c * P.hsrc_stride + (long long)m * P.hN;
-        const double sg = (m & 1) ? -w : w;
+        const double sg = ((m + s) & 1) ? -w : w;
         const double2 a = h[rp], b = h[P.hN - 1 - rp], cN = h[P.hN / 2 - 1 - rp], d = h[P.hN / 2 + rp];
         FN = make_double2(w * a.x + sg * b.x, w * a.y + sg * b.y);
         FS = make_double2(w * cN.x + sg * d.x, w * cN.y + sg * d.y);
@@ -357,6 +382,13 @@ struct hx_plan {
     } ts[8];  // spin 0, spin 2, spin 0 with half-size work-groups, spin 2 with one ring set per wave (4 ring blocks per task),
        // spin 2 / spin 0 on the vector unit (hx_legendre_valu.hip: 2 R ring blocks per task), spin 2 / spin 0 synthesis of several
        // maps per sweep (8 ring blocks per task)
+    // what the vector-unit sweep of a spin weight other than 0 and 2 needs (point transform only), built on first use and kept per
+    // weight: coefficients and scalings of its recursion (k_init_norm_s), seed factors (spin_seeds), tasks pruned by ring_mlim(lmax, s)
+    struct SpinSet {
+        hx::DevBuf cn, al, kf;
+        TaskSet ts;
+    };
+    std::map<int, SpinSet> spin_sets;
     struct FftClass { int M, first, count, big; };
     std::vector<FftClass> fft_classes;   // ring pairs grouped by in-LDS FFT length
     hx::DevBuf fft_rp_list;
@@ -379,6 +411,7 @@ namespace hx {
 // hx_plan.hip
 hx_plan *plan_create_equiangular(int N, int lmax);
 int ensure_rec2(hx_plan *pl);
+int ensure_rec_s(hx_plan *pl, int s, hx_plan::SpinSet **set);  // tables of pl->spin_sets[s] (1 <= s <= lmax)
 // hx_ring_fft.hip
 int ring_fft_plan_init(hx_plan *pl, const std::vector<int> &nsub, const std::vector<long long> &sN, const std::vector<long long> &sS);  // (hx_plan_create, behind the band-limit tables)
 int launch_ring_subdft_maps(hx_plan *pl, int nb, const double *d_maps, const double *d_pw, double2 *Y, int rp_lo = 0, int rp_hi = 0x7fffffff);  // ring pairs [rp_lo, rp_hi) only
@@ -392,6 +425,9 @@ int check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *
 int build_tasks(hx_plan *pl, int spin);
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
                    const double *d_pw, const double *d_fl, int add);
+// A spin weight that runs through the run-time-spin sweep of the vector unit, one (Q, U) field at a time: any but 0 and 2, and
+// 2 as well while HX_SPIN_GENERIC=1 (read per call).  Such a sweep exists for the equiangular plan of the point transform only.
+bool analysis_generic_spin(int spin);
 int analysis_max_comp(int spin);
 int analysis_next_batch(int spin, int remaining);
 int analysis_max_batch(int spin, int ncomp);
@@ -412,12 +448,12 @@ int analysis_stream_start(StreamSweep &s);  // zeroes the accumulation rows (que
 int analysis_stream_slab(StreamSweep &s, int k);
 int analysis_stream_end(StreamSweep &s);
 // hx_legendre_valu.hip: one map (spin 0) / one field (spin 2) per sweep on the FP64 vector unit
-int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw);
+int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic = false);
 int valu_task_blocks(int spin);      // 32-ring-pair blocks per task
 int valu_partial_cols(int spin);     // doubles per row of the partial buffer
 int valu_operand_doubles(int spin);  // doubles per (m, ring pair) of the operand array
 int valu_exec_flops(unsigned long long *v, bool reset);
-int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **ts, int blocks = 0);  // (hx_analysis.hip) task set of the vector-unit kernels (blocks: 32-ring-pair blocks per task, 0 = valu_task_blocks), built on first use
+int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **ts, int blocks = 0, bool generic = false);  // (hx_analysis.hip) task set of the vector-unit kernels (blocks: 32-ring-pair blocks per task, 0 = valu_task_blocks), built on first use
 int synth_valu_max_units(int spin);                // maps (spin 0) / fields (spin 2) per sweep of the synthesis kernel: 1, 2, .. a power of two
 int synth_valu_task_blocks(int spin, int units);   // ring blocks per task of that sweep
 int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv);

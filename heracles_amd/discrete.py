@@ -71,7 +71,9 @@ class PointSHT:
 
     def adjoint_synthesis(self, loc, values, spin=0, out=None):
         """values (ncomp, npoints) float64 at loc (npoints, 2) = (colatitude, longitude) [rad] -> alm (ncomp, nlm)
-        complex128; numpy in -> numpy out, torch device tensors in -> device tensor out."""
+        complex128; numpy in -> numpy out, torch device tensors in -> device tensor out.  ``spin`` is any weight s >= 0:
+        0 transforms every row on its own, s >= 1 reads the rows in pairs (Q, U) and returns (E, B) per pair (zero for l < s);
+        a negative ``spin`` or an odd number of rows with s >= 1 is a ``ValueError``."""
         dev = hasattr(values, "data_ptr")
         if dev:
             import torch
@@ -132,7 +134,8 @@ class HipDiscreteMapper:
 
     def map_values(self, lon, lat, data, values, spin=0):
         """Add values to alms (heracles/ducc.py:92-133): ``data += sum_p values_p conj(sY_lm(lon_p, lat_p))``.
-        float32 values are transformed to 1e-5, everything else in float64 to 1e-12, as the reference asks of ducc0."""
+        float32 values are transformed to 1e-5, everything else in float64 to 1e-12, as the reference asks of ducc0.
+        ``spin`` is any weight s >= 0, as for ducc0: rows in pairs (Q, U) -> (E, B) for s >= 1."""
         values = np.asarray(values)
         flatten = values.ndim == 1
         if flatten:

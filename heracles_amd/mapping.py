@@ -520,6 +520,10 @@ def _alm_item(key, field, catalog):
     """_item for catalog_alms; where the field reads the visibility, it must be alms (complex), as heracles/catalog/base.py:36-44 tells
     a visibility map from visibility alms."""
     it = _item(key, field, catalog, _discrete_mapper_or_error, "catalog_alms")
+    if it.kind != _VISIBILITY and (field.spin < 0 or (field.spin > 0 and it.kind != _COMPLEX)):
+        # (what hx_catalm_finish would answer with HX_ERR_ARG after the pass over the catalogue)
+        raise ValueError(f"catalog_alms: field {key[0]!r} has spin weight {field.spin}: a weight s >= 1 needs the two components of a "
+                         "ComplexField, and a negative weight has no transform")
     if (it.kind == _VISIBILITY or (it.kind == _POSITIONS and field.overdensity)) and not _is_complex(catalog.visibility):
         raise ValueError(f"catalog_alms: field {key[0]!r} needs the catalogue's visibility as alms (a complex array); a visibility map "
                          "goes with map_catalogs")
@@ -613,7 +617,8 @@ def catalog_alms(fields, catalogs, *, out=None, include=None, exclude=None, prog
     ``map_catalogs`` returns with a ``DiscreteMapper`` (heracles/fields.py:197-559 over heracles/ducc.py:92-133).  ``out[field name,
     catalogue key]`` receives ``sum_p w_p v_p conj(sY_lm(lon_p, lat_p))`` over the rows the field keeps, divided by ``nbar`` /
     ``wbar`` (``mapper.area`` is 1), less the visibility alms for ``Positions(overdensity=True)``: an array of ``mapper.create(spin=...)``,
-    or of ``mapper.create(2, spin=...)`` = (E, B) / (real, imaginary) for the two-component fields, carrying the metadata of ``create``,
+    or of ``mapper.create(2, spin=...)`` = (E, B) for a two-component field of any spin weight s >= 1 (``class X(ComplexField,
+    spin=s)``) / (real, imaginary) for one of weight 0, carrying the metadata of ``create``,
     of the catalogue and of the field.  ``out``, key order, ``include`` / ``exclude``, ``progress`` and ``device="cuda"``
     (``DeviceArray``s around complex128 tensors) are those of ``map_catalogs``.
 

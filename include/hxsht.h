@@ -305,6 +305,9 @@ int hx_alm_resample(int lmax_in, int lmax_out, int ncomp, const double *alm_in, 
  * Replaces ducc0.sht.adjoint_synthesis_general(map=values, spin=spin, lmax=lmax, loc=loc, epsilon=epsilon) as called by
  * DiscreteMapper.map_values (heracles/ducc.py:121-128):  alm[c][idx(l,m)] = sum_p map[c][p] conj(sY_lm(loc[p])), m >= 0,
  * spin 0: every row of `map` on its own; spin 2: rows (Q, U) -> (E, B) with healpy's sign conventions (those of hx_map2alm).
+ * Any other spin weight s >= 1 (ducc0 takes any): rows in pairs (Q, U) -> (E, B) in the convention of HEALPix's map2alm_spin,
+ *   (+-s)a_lm = sum_p (Q_p +- i U_p) conj((+-s)Y_lm(loc[p])),  E = -((+s)a + (-1)^s (-s)a) / 2,  B = i ((+s)a - (-1)^s (-s)a) / 2
+ * for l >= max(m, s) and zero below; s = 2 is the case above, s > lmax gives zeros.  HX_ERR_ARG: s < 0, or s > 0 with an odd ncomp.
  * loc: (npoints, 2) colatitude, longitude in radians (0 <= colatitude <= pi, else HX_ERR_ARG); map: (ncomp, npoints);
  * alm: (ncomp, nlm) complex, OVERWRITTEN (the caller adds it to its running sum, ducc.py:133); pointers host or device.
  * The object holds the non-uniform FFT of accuracy epsilon (heracles: 1e-12 for float64 values, 1e-5 for float32,
@@ -383,7 +386,8 @@ void hx_catmap_destroy(hx_catmap *ctx);
  *  hx_catalm_page:    hx_catmap_page's protocol.  Rows that add nothing (kept by no field of the group, or a zero value) cost no atomics.
  *  hx_catalm_moments: as hx_catmap_moments, the same sums in the same order (bitwise repeatable); bad[6 f + 5] counts the kept rows with a
  *                     latitude outside [-90, 90] or a non-finite coordinate, which are never added.
- *  hx_catalm_finish:  alm <- (grids of the field -> alm with the given spin: 0, or 2 for a two-component field: (E, B)) / norm - vis_alm,
+ *  hx_catalm_finish:  alm <- (grids of the field -> alm with the given spin: 0, or any s >= 1 for a two-component field: (E, B) as
+ *                     hx_pointsht_adjoint defines them; HX_ERR_ARG for s < 0 and for s > 0 on a one-component field) / norm - vis_alm,
  *                     each operation rounded on its own (vis_alm NULL: the division only).  alm: [nrow][nlm] complex, OVERWRITTEN; vis_alm:
  *                     [nlm] complex; host or device.  The grids are left as they were: a field can be finished again.
  * The spread adds with hardware float64 atomics, so the alms are NOT bit-repeatable from run to run (they agree to rounding).            */

@@ -1,4 +1,5 @@
-"""Throughput of the point transform (hx_pointsht_adjoint) at the bench's band limit: device-resident points."""
+"""Throughput of the point transform (hx_pointsht_adjoint) at the bench's band limit: device-resident points.
+LMAX, NPOINTS (comma-separated) and SPINS (comma-separated spin weights, default 0,2; any s >= 1 is one (Q, U) field) come from the environment."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, heracles_amd as hx
@@ -12,7 +13,8 @@ for n in [int(float(x)) for x in os.environ.get("NPOINTS", "1e6,1e7,1e8").split(
     loc = torch.empty((n, 2), dtype=torch.float64, device="cuda")
     loc[:, 0] = torch.acos(torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 2 - 1)
     loc[:, 1] = torch.rand(n, dtype=torch.float64, device="cuda", generator=g) * 6.283185307179586
-    for spin, nc in ((0, 1), (2, 2)):
+    for spin in [int(x) for x in os.environ.get("SPINS", "0,2").split(",")]:
+        nc = 1 if spin == 0 else 2
         v = torch.randn((nc, n), dtype=torch.float64, device="cuda", generator=g)
         out = sht.adjoint_synthesis(loc, v, spin=spin)
         hx._lib.profile_enable(True); hx._lib.profile_reset()
