@@ -1056,9 +1056,11 @@ static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_ma
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
                    const double *d_pw, const double *d_fl, int add)
 {
-    if (pl->hsrc ? analysis_generic_spin(spin) : (spin != 0 && spin != 2)) {
-        // one (Q, U) field per sweep of the run-time-spin kernel; the rings of the point transform only
-        if (!pl->hsrc) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
+    const bool generic = plan_generic_spin(pl, spin);
+    if (generic || (spin != 0 && spin != 2)) {
+        // one (Q, U) field per sweep of the run-time-spin kernel: the rings of the point transform, or resident HEALPix maps (their
+        // ring sub-DFTs first, as for spin 2); not the m-sharded route
+        if (!generic) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
         if (spin < 0 || nb < 2 || (nb & 1)) return fail(HX_ERR_ARG, "analysis_batch: %d components of spin %d", nb, spin);
         if (spin > pl->lmax) {  // no l >= s below the band limit
             if (!add) HX_HIP(hipMemsetAsync(d_alms, 0, sizeof(double2) * (size_t)pl->nlm * nb, rt().stream));

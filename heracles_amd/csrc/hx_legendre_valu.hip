@@ -1,6 +1,6 @@
 // hx_legendre_valu.hip -- Legendre / Wigner-d analysis of ONE map (spin 0) or ONE (Q,U) field (spin 2) on the FP64 vector unit.
-// A field of any other spin weight s >= 1 (point transform only) runs through the spin-2 code with s, its seeds and its tables
-// given at run time: the template value SPIN_ANY.
+// A field of any other spin weight s >= 1 (point transform and HEALPix maps) runs through the spin-2 code, analysis and synthesis,
+// with s, its seeds and its tables given at run time: the template value SPIN_ANY.
 //
 // The call the reference itself makes is a single-map transform (heracles/mapping.py:171 -> heracles/healpy.py:183-189: one
 // hp.map2alm per (field, bin)).  With two (spin 0) or four (spin 2) real columns there is nothing for a matrix instruction to
@@ -435,6 +435,9 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
 //   spin 0: the even and the odd chain have an accumulator pair each:  F_N = E + O, F_S = E - O;
 //   spin 2: P+_N = sum lambda+ a+,  P-_S = sum (-1)^(l+m) lambda+ a-,  P-_N = sum lambda- a-,  P+_S = sum (-1)^(l+m) lambda- a+,
 //           a+- = -(E +- iB);  Q = (P+ + P-) / 2,  U = (P+ - P-) / 2i.
+//   spin s (SPIN_ANY, one field per sweep): as spin 2 with lambda+- of weight +-s from l0 = max(m, s) -- seeds from spin_seeds, tables
+//           of hx_plan::SpinSet -- and a+ = -(E + iB), a- = -(-1)^s (E - iB): the sign of an odd s is applied where alpha_l a_lm is
+//           formed, everything downstream is the spin-2 code.
 // Every accumulator belongs to ONE chain.  A scaled chain (exponent < 0) is not masked inside the loop: what it adds between two
 // checks is dropped at the next check (its accumulators are zeroed as long as it is not live: it has never contributed before),
 // and at the end.  Output Fv[m][ring pair][NV]: (N_re, N_im, S_re, S_im) per component -- spin 2: Q then U.
@@ -458,6 +461,8 @@ struct SynValuParams {
     const LegTask *__restrict__ tasks;
     const double2 *__restrict__ alm;  // component c at + c alm_stride: spin 0: the maps' alms; spin 2: (E, B) per field
     long long alm_stride;
+    const double *__restrict__ kfs;   // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinSet::kf)
+    int s;
     double *__restrict__ Fv;          // [m][rp][NV]: component c = (N_re, N_im, S_re, S_im) at 4 c (spin 2: Q, U of field b at 8 b)
 };
 
@@ -475,8 +480,8 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
     const PlanDev &P = A.P;
     const LegTask task = A.tasks[blockIdx.x];
     const int m = task.m, lmax = P.lmax, lane = threadIdx.x;
-    const int l0 = SPIN == 0 ? m : (m > 2 ? m : 2);
-    const int off = (l0 + m) & 1;        // parity of l + m at the first l (spin 2, m = 1 only)
+    const int l0 = SPIN == 0 ? m : (SPIN == 2 ? (m > 2 ? m : 2) : (m > A.s ? m : A.s));
+    const int off = (l0 + m) & 1;        // parity of l + m at the first l (spin 2: m = 1 only; spin s: m < s)
     const long long cb = almidx(lmax, 0, m);
     const int coff = SPIN == 0 ? 0 : 1;  // spin-2 coefficients are indexed by the target l
 
@@ -506,7 +511,8 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
                 vc[r][1] = b.v; sc[r][1] = b.e;
             } else {
                 SVal sp, sm;
-                spin2_seeds(m, P.sth[rp], P.omz[rp], P.kfac2[m], sp, sm);
+                if (SPIN == 2) spin2_seeds(m, P.sth[rp], P.omz[rp], P.kfac2[m], sp, sm);
+                else spin_seeds(A.s, m, P.sth[rp], P.omz[rp], A.kfs[m], sp, sm);
                 vc[r][0] = sp.v; sc[r][0] = sp.e;
                 vc[r][1] = sm.v; sc[r][1] = sm.e;
             }
@@ -589,8 +595,9 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
                 } else {
                     const double2 E = in ? A.alm[2 * b * A.alm_stride + cb + l] : make_double2(0.0, 0.0);
                     const double2 B = in ? A.alm[(2 * b + 1) * A.alm_stride + cb + l] : make_double2(0.0, 0.0);
+                    const double am = (SPIN == SPIN_ANY && (A.s & 1)) ? -al : al;                              // a- of an odd weight: -(-1)^s
                     apre[b * NA1 + 0] = al * (-E.x + B.y); apre[b * NA1 + 1] = al * (-E.y - B.x);              // a+ = -(E + iB)
-                    apre[b * NA1 + 2 % NA1] = al * (-E.x - B.y); apre[b * NA1 + 3 % NA1] = al * (-E.y + B.x);  // a- = -(E - iB)
+                    apre[b * NA1 + 2 % NA1] = am * (-E.x - B.y); apre[b * NA1 + 3 % NA1] = am * (-E.y + B.x);  // a- = -(E - iB)
                 }
             }
         }
@@ -694,7 +701,7 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
     }
     // ---- ring modes of this m ----
     double *fm = A.Fv + (long long)m * P.nrp_pad * NV;
-    const double ssgn = (SPIN == 2 && off) ? -1.0 : 1.0;
+    const double ssgn = (SPIN != 0 && off) ? -1.0 : 1.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         drop(r, 0);  // chains that never became live
@@ -732,28 +739,38 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
 // Fv of `units` maps (spin 0: 1, 2 or 4) / fields (spin 2: 1 or 2) whose alms start at d_alm; ts = the task set of
 // synth_valu_task_blocks(spin, units) ring blocks per task; rings outside the task list (pruned) stay zero
 template <int SPIN, int NB>
-static int launch_synth_valu_t(hx_plan *pl, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv)
+static int launch_synth_valu_t(hx_plan *pl, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, int s)
 {
     hipStream_t st = rt().stream;
     constexpr int NV = SynValuCfg<SPIN, NB>::NV;
     HX_HIP(hipMemsetAsync(d_Fv, 0, sizeof(double) * (size_t)(pl->lmax + 1) * pl->nrp_pad * NV, st));
     SynValuParams A;
     A.P = pl->dev(); A.tasks = ts.d_tasks.as<LegTask>(); A.alm = d_alm; A.alm_stride = pl->nlm; A.Fv = d_Fv;
+    A.kfs = nullptr; A.s = s;
     const double2 *cn = SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
     const double *al = SPIN == 0 ? pl->al0.as<double>() : pl->al2.as<double>();
+    if (SPIN == SPIN_ANY) {  // tables and seed factors of this weight: never those of spin 2
+        hx_plan::SpinSet *set = nullptr;
+        HX_TRY(ensure_rec_s(pl, s, &set));
+        A.kfs = set->kf.as<double>(); cn = set->cn.as<double2>(); al = set->al.as<double>();
+    }
     ProfScope ps("legendre_synthesis");
     ProfScope ps2("legendre_synth_valu");
     hipLaunchKernelGGL((k_legendre_synth_valu<SPIN, NB>), dim3((unsigned)ts.tasks.size()), dim3(64), 0, st, A, cn, al);
     HX_HIP(hipGetLastError());
     return HX_OK;
 }
-int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv)
+int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic)
 {
-    if (spin == 0 && units == 1) return launch_synth_valu_t<0, 1>(pl, ts, d_alm, d_Fv);
-    if (spin == 0 && units == 2) return launch_synth_valu_t<0, 2>(pl, ts, d_alm, d_Fv);
-    if (spin == 0 && units == 4) return launch_synth_valu_t<0, 4>(pl, ts, d_alm, d_Fv);
-    if (spin == 2 && units == 1) return launch_synth_valu_t<2, 1>(pl, ts, d_alm, d_Fv);
-    if (spin == 2 && units == 2) return launch_synth_valu_t<2, 2>(pl, ts, d_alm, d_Fv);
+    if (generic) {  // ts: the task set of valu_tasks(pl, spin, ., ., true)
+        if (spin >= 1 && spin <= pl->lmax && units == 1) return launch_synth_valu_t<SPIN_ANY, 1>(pl, ts, d_alm, d_Fv, spin);
+        return fail(HX_ERR_ARG, "launch_synth_valu: %d units of spin %d on the run-time-spin sweep", units, spin);
+    }
+    if (spin == 0 && units == 1) return launch_synth_valu_t<0, 1>(pl, ts, d_alm, d_Fv, 0);
+    if (spin == 0 && units == 2) return launch_synth_valu_t<0, 2>(pl, ts, d_alm, d_Fv, 0);
+    if (spin == 0 && units == 4) return launch_synth_valu_t<0, 4>(pl, ts, d_alm, d_Fv, 0);
+    if (spin == 2 && units == 1) return launch_synth_valu_t<2, 1>(pl, ts, d_alm, d_Fv, 2);
+    if (spin == 2 && units == 2) return launch_synth_valu_t<2, 2>(pl, ts, d_alm, d_Fv, 2);
     return fail(HX_ERR_ARG, "launch_synth_valu: %d units of spin %d", units, spin);
 }
 

@@ -10,12 +10,13 @@
 
 using namespace hx;
 
-int hx::check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b)
+int hx::check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b, bool any_spin)
 {
     if (!pl || !a || !b) return fail(HX_ERR_ARG, "null plan or buffer");
     if (pl->nside < 1) return fail(HX_ERR_ARG, "not a HEALPix plan");
-    if (spin != 0 && spin != 2) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
-    if (ncomp < 1 || (spin == 2 && (ncomp & 1))) return fail(HX_ERR_ARG, "bad component count %d for spin %d", ncomp, spin);
+    if (spin < 0 && any_spin) return fail(HX_ERR_ARG, "negative spin weight %d", spin);
+    if (spin != 0 && spin != 2 && !any_spin) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
+    if (ncomp < 1 || (spin >= 1 && (ncomp & 1))) return fail(HX_ERR_ARG, "bad component count %d for spin %d", ncomp, spin);
     return HX_OK;
 }
 
@@ -227,13 +228,14 @@ extern "C" int hx_map2alm(hx_plan *pl, int spin, int ncomp, const double *maps, 
                           const double *ring_weights, const double *pix_weights, const double *fl, int niter)
 {
     HX_TRY(ensure_ready());
-    HX_TRY(check_sht_args(pl, spin, ncomp, maps, alms));
+    HX_TRY(check_sht_args(pl, spin, ncomp, maps, alms, true));
     if (niter < 0) return fail(HX_ERR_ARG, "niter < 0");
     InView vmaps, vrw, vpw, vfl;
     OutView valms;
     // Host maps without iterations go through the upload pipeline of hx_map2alm_multi (one job): sweep k + 1 is staged (pageable ->
     // pinned -> HBM, second stream, three plan-owned buffers) while the GPU transforms sweep k
-    if (niter == 0 && !is_device_ptr(maps) && copy_stream() != nullptr)
+    // (a weight on the run-time-spin sweep is uploaded whole and transformed resident: the pipeline's sweeps are not built for it)
+    if (niter == 0 && !is_device_ptr(maps) && copy_stream() != nullptr && !analysis_generic_spin(spin))
         return map2alm_multi_impl(pl, 1, &spin, &ncomp, &maps, nullptr, &alms, ring_weights, pix_weights, &fl);
     HX_TRY(vmaps.bind(maps, sizeof(double) * (size_t)ncomp * pl->npix));
     HX_TRY(vrw.bind(ring_weights, sizeof(double) * pl->nrp));

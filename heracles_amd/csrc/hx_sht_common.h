@@ -382,7 +382,7 @@ struct hx_plan {
     } ts[8];  // spin 0, spin 2, spin 0 with half-size work-groups, spin 2 with one ring set per wave (4 ring blocks per task),
        // spin 2 / spin 0 on the vector unit (hx_legendre_valu.hip: 2 R ring blocks per task), spin 2 / spin 0 synthesis of several
        // maps per sweep (8 ring blocks per task)
-    // what the vector-unit sweep of a spin weight other than 0 and 2 needs (point transform only), built on first use and kept per
+    // what the vector-unit sweeps of a spin weight other than 0 and 2 need (analysis and synthesis), built on first use and kept per
     // weight: coefficients and scalings of its recursion (k_init_norm_s), seed factors (spin_seeds), tasks pruned by ring_mlim(lmax, s)
     struct SpinSet {
         hx::DevBuf cn, al, kf;
@@ -420,14 +420,16 @@ int classify_pixel_weights(hx_plan *pl, const double *d_pw);
 // hx_synthesis.hip
 int synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, double *d_maps, const double *d_ref);  // d_ref: maps <- ref - synthesised
 // hx_map2alm.hip
-int check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b);
+int check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b, bool any_spin = false);  // any_spin: a weight other than 0 and 2 is served (hx_map2alm, hx_alm2map)
 // hx_analysis.hip
 int build_tasks(hx_plan *pl, int spin);
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
                    const double *d_pw, const double *d_fl, int add);
 // A spin weight that runs through the run-time-spin sweep of the vector unit, one (Q, U) field at a time: any but 0 and 2, and
-// 2 as well while HX_SPIN_GENERIC=1 (read per call).  Such a sweep exists for the equiangular plan of the point transform only.
+// 2 as well while HX_SPIN_GENERIC=1 (read per call).  Such a sweep, analysis and synthesis, exists for the equiangular plan of the
+// point transform and for resident HEALPix maps (plan_generic_spin); not for the m-sharded route or the streamed uploads.
 bool analysis_generic_spin(int spin);
+inline bool plan_generic_spin(const hx_plan *pl, int spin) { return (pl->hsrc || (pl->nside >= 1 && !pl->nssrc)) && analysis_generic_spin(spin); }
 int analysis_max_comp(int spin);
 int analysis_next_batch(int spin, int remaining);
 int analysis_max_batch(int spin, int ncomp);
@@ -456,7 +458,7 @@ int valu_exec_flops(unsigned long long *v, bool reset);
 int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **ts, int blocks = 0, bool generic = false);  // (hx_analysis.hip) task set of the vector-unit kernels (blocks: 32-ring-pair blocks per task, 0 = valu_task_blocks), built on first use
 int synth_valu_max_units(int spin);                // maps (spin 0) / fields (spin 2) per sweep of the synthesis kernel: 1, 2, .. a power of two
 int synth_valu_task_blocks(int spin, int units);   // ring blocks per task of that sweep
-int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv);
+int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic = false);  // generic: the run-time-spin sweep (one field, ts of valu_tasks(.., true))
 // hx_synth_duo.hip: up to 20 maps / 10 fields per sweep on the matrix unit; Fv[m][rp][synth_duo_rowlen] in the lane order of that kernel
 int synth_duo_max_units(int spin);
 int synth_duo_rowlen(int spin, int units);

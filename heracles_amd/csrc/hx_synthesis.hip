@@ -119,12 +119,13 @@ using namespace hx;
 // kernel it replaces took 100 / 217 ms for one spin-0 map / spin-2 field at nside 4096 against 19 / 57, and 201 / 653 ms for ten
 // against 187 / 570).  If d_ref != NULL the output is the residual ref - synth (Jacobi iteration). ----
 // small batches: one sweep of the vector-unit kernel per four maps / two fields (they share the recursion), then the rest
-static int synthesis_batch_valu(hx_plan *pl, int spin, int nb, const double2 *d_alms, double *d_maps, const double *d_ref)
+// generic: one field per sweep of the run-time-spin instantiation, with the tables and the task set of its weight
+static int synthesis_batch_valu(hx_plan *pl, int spin, int nb, const double2 *d_alms, double *d_maps, const double *d_ref, bool generic = false)
 {
     hipStream_t st = rt().stream;
     const int cpu = spin ? 2 : 1;
     PlanDev P = pl->dev();
-    const int umax = synth_valu_max_units(spin);
+    const int umax = generic ? 1 : synth_valu_max_units(spin);
     // ring modes and ring spectra live in the analysis' operand buffer F, as in the batched path (F is idle during a synthesis, and a plan
     // that has run a batched synthesis holds most of the HBM in it already: separate buffers failed to allocate at nside 8192)
     const size_t fv_pad = (sizeof(double) * (size_t)(pl->lmax + 1) * pl->nrp_pad * 4 * cpu * umax + 255) & ~(size_t)255;
@@ -136,8 +137,8 @@ static int synthesis_batch_valu(hx_plan *pl, int spin, int nb, const double2 *d_
         while (units * cpu > nb - c0) units >>= 1;
         const int nc = units * cpu;
         hx_plan::TaskSet *ts = nullptr;
-        HX_TRY(valu_tasks(pl, spin, &ts, synth_valu_task_blocks(spin, units)));
-        HX_TRY(launch_synth_valu(pl, spin, units, *ts, d_alms + (size_t)c0 * pl->nlm, fsyn));
+        HX_TRY(valu_tasks(pl, spin, &ts, synth_valu_task_blocks(spin, units), generic));
+        HX_TRY(launch_synth_valu(pl, spin, units, *ts, d_alms + (size_t)c0 * pl->nlm, fsyn, generic));
         ProfScope ps("ring_fft");
         hipLaunchKernelGGL(k_synth_spectrum_v, dim3((pl->nrp + 3) / 4), dim3(256), 0, st, P, fsyn, nc, pl->lmax, zc, (const int *)nullptr, pl->nrp);
         // inverse sub-DFTs whose read-out writes the pixels (or the residual ref - synthesised of a Jacobi iteration) itself
@@ -152,6 +153,19 @@ int hx::synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, do
 {
     hipStream_t st = rt().stream;
     const int cpu = spin ? 2 : 1;  // components per unit (map / field)
+    const bool generic = plan_generic_spin(pl, spin);
+    if (generic || (spin != 0 && spin != 2)) {
+        // a spin weight other than 0 and 2 (HX_SPIN_GENERIC=1: 2 as well): one sweep of the run-time-spin kernel per field
+        if (!generic || pl->hsrc) return fail(HX_ERR_UNSUPPORTED, "spin-%d maps not yet supported", spin);
+        if (spin < 0 || nb < 2 || (nb & 1)) return fail(HX_ERR_ARG, "synthesis_batch: %d components of spin %d", nb, spin);
+        if (spin > pl->lmax) {  // no l >= s below the band limit: zero maps, i.e. the residual is the reference
+            const size_t bytes = sizeof(double) * (size_t)pl->npix * nb;
+            if (d_ref) HX_HIP(hipMemcpyAsync(d_maps, d_ref, bytes, hipMemcpyDeviceToDevice, st));
+            else HX_HIP(hipMemsetAsync(d_maps, 0, bytes, st));
+            return HX_OK;
+        }
+        return synthesis_batch_valu(pl, spin, nb, d_alms, d_maps, d_ref, true);
+    }
     PlanDev P = pl->dev();
     // batches of >= 5 maps / >= 3 fields: sweeps of up to 20 maps / 10 fields on the matrix unit (hx_synth_duo.hip).  Their ring
     // modes (Fv) and ring spectra (conj Z) live in the analysis' operand buffer F, which is idle during a synthesis: a Jacobi iteration
@@ -219,7 +233,7 @@ int hx::synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, do
 extern "C" int hx_alm2map(hx_plan *pl, int spin, int ncomp, const double *alms, double *maps)
 {
     HX_TRY(ensure_ready());
-    HX_TRY(check_sht_args(pl, spin, ncomp, alms, maps));
+    HX_TRY(check_sht_args(pl, spin, ncomp, alms, maps, true));
     InView valms;
     OutView vmaps;
     HX_TRY(valms.bind(alms, sizeof(double2) * (size_t)ncomp * pl->nlm));

@@ -20,6 +20,9 @@ from .core import DeviceArray, update_metadata
 
 def pixel_window(nside, lmax, pixwin=None):
     """(pw_T, pw_P) up to lmax: explicit arrays, a callable(nside, lmax), or healpy's table."""
+    if isinstance(pixwin, dict):
+        # windows by spin weight: the pair of spin 0 and 2 if both are given, else healpy's table
+        pixwin = (pixwin[0], pixwin[2]) if 0 in pixwin and 2 in pixwin else None
     if pixwin is not None:
         if callable(pixwin):
             pw0, pw2 = pixwin(nside, lmax)
@@ -231,10 +234,22 @@ class HipHealpixMapper:
         map_values(self.__nside, lon, lat, data, values)
 
     def _fl(self, spin):
+        """1 / pixel window of the field's spin weight from l = |spin| on, or None without deconvolution.  healpy ships windows
+        for spin 0 and 2 only; a window of any weight may be given as ``pixwin={spin: array}``.  A weight without a window is
+        an error: the spin-2 window is never used in its place."""
         if not self.__deconv:
             return None
-        pw0, pw2 = pixel_window(self.__nside, self.__lmax, self.pixwin)
-        pw = pw0 if spin == 0 else pw2
+        if isinstance(self.pixwin, dict) and spin in self.pixwin:
+            pw = np.asarray(self.pixwin[spin], dtype=float)
+            if pw.shape[-1] < self.__lmax + 1:
+                raise ValueError("pixel window shorter than lmax+1")
+            pw = pw[: self.__lmax + 1]
+        elif spin in (0, 2):
+            pw0, pw2 = pixel_window(self.__nside, self.__lmax, self.pixwin)
+            pw = pw0 if spin == 0 else pw2
+        else:
+            raise ValueError(f"no pixel window for spin-{spin} fields: HEALPix tabulates windows for spin 0 and 2 only; use "
+                             f"deconvolve=False, or give one as pixwin={{{spin}: ...}}")
         fl = np.ones(self.__lmax + 1)
         fl[abs(spin):] /= pw[abs(spin):]
         return fl
@@ -254,8 +269,11 @@ class HipHealpixMapper:
                     raise FileNotFoundError(f"no pixel-weight file {weights_filename(self.__nside)} under datapath {path!r}")
 
     def transform(self, data, spin=0):
-        """Spherical harmonic transform of HEALPix maps; heracles/healpy.py:162-203."""
-        if spin not in (0, 2):
+        """Spherical harmonic transform of HEALPix maps; heracles/healpy.py:162-203.  Beyond the reference: a field of any spin
+        weight s >= 1 given as ``(..., 2, npix)`` (Q, U) gives (E, B) in the convention of HEALPix's ``map2alm_spin``."""
+        shape = tuple(data.shape) if hasattr(data, "shape") else np.shape(data)
+        if spin < 0 or (spin not in (0, 2) and (len(shape) < 2 or shape[-2] != 2)):
+            # a weight s >= 1 other than 2 is served for fields of two components (Q, U) only
             raise NotImplementedError(f"spin-{spin} maps not yet supported")
         fl = self._fl(spin)
         self._load_weights()
@@ -269,14 +287,14 @@ class HipHealpixMapper:
         if hasattr(data, "data_ptr"):
             # device-resident maps (e.g. accumulated by map_values on the GPU): alms stay in HBM; a torch
             # tensor cannot carry dtype metadata, so none is attached
-            if spin == 2 and (data.ndim < 2 or data.shape[-2] != 2):
-                raise ValueError("spin-2 maps must have shape (..., 2, npix)")
+            if spin >= 1 and (data.ndim < 2 or data.shape[-2] != 2):
+                raise ValueError(f"spin-{spin} maps must have shape (..., 2, npix)")
             return plan.map2alm(data, spin, ring_weights=self.ring_weights, pix_weights=self.pixel_weights,
                                 fl=fl, niter=self.niter)
         md = data.dtype.metadata or {}
         maps = np.ascontiguousarray(_native(data), dtype=np.float64)
-        if spin == 2 and (maps.ndim < 2 or maps.shape[-2] != 2):
-            raise ValueError("spin-2 maps must have shape (..., 2, npix)")
+        if spin >= 1 and (maps.ndim < 2 or maps.shape[-2] != 2):
+            raise ValueError(f"spin-{spin} maps must have shape (..., 2, npix)")
         alm = plan.map2alm(maps, spin, ring_weights=self.ring_weights,
                            pix_weights=self.pixel_weights, fl=fl, niter=self.niter)
         update_metadata(alm, **{**md, "deconv": self.__deconv})
@@ -286,10 +304,12 @@ class HipHealpixMapper:
         """Batched transform of a list of maps (the loop of heracles/mapping.py:151-172 as one call): the arrays go to
         ``hx_map2alm_list`` as they are -- no stacked copy on the host, one upload pipeline across spins (``niter = 0``) or one
         resident batch per spin (``niter > 0``).  ``device="cuda"``: the alms stay in HBM and come back as ``DeviceArray``s (what
-        ``angular_power_spectra`` takes without another PCIe round trip); default: numpy arrays, as the reference returns."""
+        ``angular_power_spectra`` takes without another PCIe round trip); default: numpy arrays, as the reference returns.
+        Fields of a spin weight other than 0 and 2 are transformed one by one (``Plan.map2alm``), in the same call and order."""
         for sp in spins:
-            if sp not in (0, 2):
+            if sp < 0:
                 raise NotImplementedError(f"spin-{sp} maps not yet supported")
+        fls = {sp: self._fl(sp) for sp in set(spins) if sp not in (0, 2)}
         self._load_weights()
         if self.pixel_weights is None and self.ring_weights is None:
             _warn_unit_weights()
@@ -305,7 +325,8 @@ class HipHealpixMapper:
 
             outs = [torch.empty((nlm,) if sp == 0 else (2, nlm), dtype=torch.complex128, device=device) for sp in spins]
         alms = plan.map2alm_list(native, spins, outs=outs, ring_weights=self.ring_weights, pix_weights=self.pixel_weights,
-                                 fl0=self._fl(0), fl2=self._fl(2), niter=self.niter)
+                                 fl0=self._fl(0) if 0 in spins else None, fl2=self._fl(2) if 2 in spins else None, niter=self.niter,
+                                 fls=fls)
         out = []
         for m, a, sp in zip(maps, alms, spins):
             md = {**((m.dtype.metadata or {}) if isinstance(m, (np.ndarray, DeviceArray)) else {"spin": sp}), "deconv": self.__deconv}

@@ -94,7 +94,9 @@ class Plan:
     # -- transforms ---------------------------------------------------------------
     def map2alm(self, maps, spin=0, *, ring_weights=None, pix_weights=None, fl=None,
                 niter=0, out=None):
-        """maps (..., npix) -> alm (..., nlm).  spin 2: the leading axis pairs (Q, U) -> (E, B)."""
+        """maps (..., npix) -> alm (..., nlm).  spin 2: the leading axis pairs (Q, U) -> (E, B); any other spin weight s >= 1:
+        maps (..., 2, npix) -> (..., 2, nlm), one sweep of the run-time-spin kernels per field (an odd number of components, or a
+        negative spin, is the library's HX_ERR_ARG)."""
         maps = self._prep(maps, np.float64)
         lead = tuple(maps.shape[:-1])
         if maps.shape[-1] != self.npix:
@@ -143,11 +145,33 @@ class Plan:
         _lib.check(_lib.load().hx_map2alm_multi(self._h, n, spins, ncomps, pm, pa, _lib.ptr(rw), _lib.ptr(pw), pf))
         return outs
 
-    def map2alm_list(self, maps, spins, *, outs=None, ring_weights=None, pix_weights=None, fl0=None, fl2=None, niter=0):
+    def map2alm_list(self, maps, spins, *, outs=None, ring_weights=None, pix_weights=None, fl0=None, fl2=None, niter=0, fls=None):
+        """``_map2alm_list`` for the maps of spin 0 and 2, all in one call; a field of any other spin weight s >= 1 goes through
+        ``map2alm``, one by one, with the filter ``fls[s]`` (``fls``: a dict, no entry = no filter).  Results in the order of
+        ``maps``; ``outs[i]``, if given, receives map i's alms."""
+        spins = [int(s) for s in spins]
+        if any(s < 0 for s in spins):
+            raise NotImplementedError(f"spin-{min(spins)} maps not yet supported")
+        listed = [i for i, s in enumerate(spins) if s in (0, 2)]
+        res = [None] * len(spins)
+        if listed:
+            got = self._map2alm_list([maps[i] for i in listed], [spins[i] for i in listed],
+                                     outs=None if outs is None else [outs[i] for i in listed], ring_weights=ring_weights,
+                                     pix_weights=pix_weights, fl0=fl0, fl2=fl2, niter=niter)
+            for i, a in zip(listed, got):
+                res[i] = a
+        for i, s in enumerate(spins):
+            if s not in (0, 2):
+                res[i] = self.map2alm(maps[i], s, ring_weights=ring_weights, pix_weights=pix_weights, fl=(fls or {}).get(s),
+                                      niter=niter, out=None if outs is None else outs[i])
+        return res
+
+    def _map2alm_list(self, maps, spins, *, outs=None, ring_weights=None, pix_weights=None, fl0=None, fl2=None, niter=0):
         """The transform loop of ``heracles.transform`` (heracles/mapping.py:151-172) as one call over SEPARATE arrays: ``maps[i]``
         is ``(npix,)`` for spin 0 or ``(2, npix)`` (Q, U) for spin 2, numpy or device; returns one alm array per map (``(nlm,)`` /
         ``(2, nlm)``).  The maps are gathered into the upload pipeline sweep by sweep (no stacked host copy), spin-2 fields first;
-        with ``niter > 0`` the maps of a spin are gathered into one device array and iterated as a batch."""
+        with ``niter > 0`` the maps of a spin are gathered into one device array and iterated as a batch.  ``hx_map2alm_list``
+        serves spin 0 and 2 only (any other spin: ``NotImplementedError``)."""
         import ctypes as C
 
         n = len(maps)
@@ -176,6 +200,7 @@ class Plan:
         return res
 
     def alm2map(self, alms, spin=0, *, out=None):
+        """alm (..., nlm) -> maps (..., npix); a spin weight s >= 1 other than 2: (E, B) (..., 2, nlm) -> (Q, U) (..., 2, npix)."""
         alms = self._prep(alms, np.complex128)
         lead = tuple(alms.shape[:-1])
         if alms.shape[-1] != self.nlm:

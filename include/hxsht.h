@@ -106,8 +106,12 @@ int hx_plan_executed_flops(hx_plan *plan, int spin, int ncomp, double *out2);
  * bench.py's roofline.achieved is these / the kernels' HIP-event time; it agrees with the SQ_INSTS_VALU_MFMA_F64 counter. */
 int hx_executed_flops(double *out2, int reset);
 
-/* maps  : [ncomp][npix] double; spin 2: components come in (Q,U) pairs, ncomp even
- * alms  : [ncomp][nlm] complex; spin 2: (E,B) pairs
+/* spin  : any spin weight s >= 0 (negative: HX_ERR_ARG).  0 and 2 have kernels of their own, also for batches; any other
+ *         weight runs one sweep per field of the vector-unit kernels that take s at run time (analysis and synthesis, every niter),
+ *         in the convention of HEALPix's map2alm_spin / alm2map_spin (rows l < s of the alms are zero / not read; s > lmax: zero alms /
+ *         zero maps).  HX_SPIN_GENERIC=1 (read per call; a test hook) sends spin 2 through those sweeps as well.
+ * maps  : [ncomp][npix] double; spin s >= 1: components come in (Q,U) pairs, ncomp even (odd: HX_ERR_ARG)
+ * alms  : [ncomp][nlm] complex; spin s >= 1: (E,B) pairs
  * ring_weights : NULL or [2*nside] quadrature weights of ring pairs (north ring 1..2nside)
  * pix_weights  : NULL or [npix] per-pixel weights (healpy use_pixel_weights=True data).  An array that repeats over the four
  *                quadrants of every ring and from north to south -- healpy's weights do -- is recognised per call and read
@@ -122,7 +126,8 @@ int hx_alm2map(hx_plan *plan, int spin, int ncomp, const double *alms, double *m
 /* The loop of heracles/mapping.py:151-172 (one transform per (field, bin) map) as ONE call over njobs transforms
  * (spins[j], ncomps[j], maps[j], alms[j], fls[j] as in hx_map2alm; fls may be NULL; niter = 0): host maps of all jobs share one
  * upload pipeline that the transforms follow slab of rings by slab of rings, so that the call costs its PCIe time plus a twelfth of one
- * sweep.  Put large jobs first.  Results are bit-identical to those of njobs hx_map2alm calls on the same (host or device) maps. */
+ * sweep.  Put large jobs first.  Results are bit-identical to those of njobs hx_map2alm calls on the same (host or device) maps.
+ * Spin 0 and 2 only (as hx_map2alm_list, hx_ring_modes / hx_legendre_from_modes): any other weight is HX_ERR_UNSUPPORTED here. */
 int hx_map2alm_multi(hx_plan *plan, int njobs, const int *spins, const int *ncomps, const double *const *maps, double *const *alms,
                      const double *ring_weights, const double *pix_weights, const double *const *fls);
 /* The same for SEPARATE arrays, as heracles holds them (heracles/mapping.py:151-172: one array per (field, bin)): map i is
