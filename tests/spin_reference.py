@@ -83,8 +83,19 @@ def spin_lambda(t, m, lmax, theta):
     return out
 
 
-def points2alm_spin(theta, phi, values, lmax, s):
-    """values (ncomp, npoints), ncomp even, rows (Q, U) -> (E, B) alms (ncomp, nlm) complex128, m-major."""
+def _orders(orders, lmax):
+    """All orders 0 .. lmax, or the given ones in ascending order, each once."""
+    if orders is None:
+        return range(lmax + 1)
+    ms = sorted({int(m) for m in orders})
+    if ms and (ms[0] < 0 or ms[-1] > lmax):
+        raise ValueError("orders: 0 <= m <= lmax")
+    return ms
+
+
+def points2alm_spin(theta, phi, values, lmax, s, orders=None):
+    """values (ncomp, npoints), ncomp even, rows (Q, U) -> (E, B) alms (ncomp, nlm) complex128, m-major.  ``orders``: an iterable
+    of m; only those orders are computed, the other rows stay zero (a long transform on a sample of m costs what the sample costs)."""
     if s < 1:
         raise ValueError("points2alm_spin: s >= 1")
     values = np.asarray(values, dtype=ld)
@@ -95,7 +106,7 @@ def points2alm_spin(theta, phi, values, lmax, s):
     alm = np.zeros((values.shape[0], nlm), dtype=np.complex128)
     q, u = values[0::2], values[1::2]
     sgn = -1 if s & 1 else 1
-    for m in range(lmax + 1):
+    for m in _orders(orders, lmax):
         l0 = max(m, s)
         if l0 > lmax:
             continue

@@ -16,11 +16,12 @@ s = 2 and to ``points2alm_spin`` (adjointness) before any device result is compa
 
 import numpy as np
 
-from spin_reference import ld, spin_lambda
+from spin_reference import _orders, ld, spin_lambda
 
 
-def alm2points_spin(theta, phi, alm, lmax, s):
-    """alm (ncomp, nlm) complex, ncomp even, rows (E, B) -> values (ncomp, npoints) float64, rows (Q, U)."""
+def alm2points_spin(theta, phi, alm, lmax, s, orders=None):
+    """alm (ncomp, nlm) complex, ncomp even, rows (E, B) -> values (ncomp, npoints) float64, rows (Q, U).  ``orders``: an iterable
+    of m; only those orders of the alms are read, as if every other row were zero."""
     if s < 1:
         raise ValueError("alm2points_spin: s >= 1")
     alm = np.asarray(alm)
@@ -29,7 +30,7 @@ def alm2points_spin(theta, phi, alm, lmax, s):
     theta, phi = np.asarray(theta, dtype=ld), np.asarray(phi, dtype=ld)
     out = np.zeros((alm.shape[0], theta.size), dtype=ld)
     sgn = -1 if s & 1 else 1
-    for m in range(lmax + 1):
+    for m in _orders(orders, lmax):
         l0 = max(m, s)
         if l0 > lmax:
             continue

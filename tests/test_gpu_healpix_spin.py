@@ -10,6 +10,7 @@ import pytest
 
 import helpers
 from oracle import hxoracle as oracle
+from healpix_pixels import special_pixels as _special_pixels
 from spin_reference import points2alm_spin
 from spin_synthesis_reference import alm2points_spin, harmonic_inner
 
@@ -40,24 +41,6 @@ def _ring_of_pixels(nside):
     assert start.size == 4 * nside - 1
     ring = np.searchsorted(start, np.arange(theta.size), side="right") - 1
     return ring, start
-
-
-def _special_pixels(nside, rng, n=400):
-    """At most n pixels where the ring geometry changes: all four pixels of the first and of the last ring; on ring nside (the
-    cap meets the belt), on two neighbouring belt rings (one shifted, one not), on the equator and on the mirror of ring nside
-    the first and the last pixel and a few between; random pixels for the rest.  Every pixel of a small map."""
-    npix = 12 * nside * nside
-    if npix <= n:
-        return np.arange(npix)
-    _, start = _ring_of_pixels(nside)
-    end = np.concatenate([start[1:], [npix]])
-    pix = [0, 1, 2, 3, npix - 4, npix - 3, npix - 2, npix - 1]
-    for r in (nside - 2, nside - 1, nside, nside + 1, 2 * nside - 1, 3 * nside - 1, 3 * nside):  # (0-based ring numbers)
-        pix += [start[r], end[r] - 1]
-        pix += list(rng.integers(start[r], end[r], 6))
-    pix = np.unique(np.array(pix, dtype=np.int64))
-    rest = np.setdiff1d(rng.choice(npix, n, replace=False), pix)[: n - pix.size]
-    return np.sort(np.concatenate([pix, rest]))
 
 
 _CASES = {}
@@ -121,11 +104,27 @@ def test_map2alm_against_direct_sum(nside, lmax, s):
     assert _low_rows_are_zero(got, lmax, s)
 
 
+# weights with more than three orders m < s (the m < s seeds of spin_seeds, chains from l0 = s > m), even and odd; (8, 8) with
+# s = 8: s = lmax, one row per order
+@pytest.mark.parametrize("nside,lmax,s", [(n, l, s) for s in (4, 5, 8) for n, l in ((4, 8), (8, 23), (16, 24))] + [(8, 8, 8)])
+def test_map2alm_higher_weights_against_direct_sum(nside, lmax, s):
+    import heracles_amd as hx
+
+    maps, want = _analysis_case(nside, lmax, s)
+    plan = hx.Plan(nside, lmax)
+    got = plan.map2alm(maps, s)
+    plan.close()
+    assert got.shape == want.shape and np.abs(want).max() > 0
+    print(f"nside {nside} lmax {lmax} s {s}: err {_err(got, want):.3e}")
+    assert _err(got, want) < TOL
+    assert _low_rows_are_zero(got, lmax, s)
+
+
 # ---- 2. scaled chains and ring pruning ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("s", [1, 3])
+@pytest.mark.parametrize("s", [1, 3, 8])
 def test_map2alm_scaled_chains_and_pruning(s):
-    """nside 128 / lmax 200: sin^m(theta) underflows on the polar rings and ring_mlim(lmax, s) prunes; a map that is non-zero in
-    at most 400 pixels (poles, cap / belt boundary, shifted and unshifted belt rings, equator, ring ends) keeps the direct sum cheap."""
+    """nside 128 / lmax 200: sin^m(theta) underflows on the polar rings and ring_mlim(lmax, s) prunes (it depends on s); a map that is
+    non-zero in at most 400 pixels (poles, cap / belt boundary, shifted and unshifted belt rings, equator, ring ends) keeps the direct sum cheap."""
     import heracles_amd as hx
 
     nside, lmax = 128, 200
@@ -138,7 +137,7 @@ def test_map2alm_scaled_chains_and_pruning(s):
 
 
 # ---- 3. the two front ends agree ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("s", [1, 3])
+@pytest.mark.parametrize("s", [1, 3, 4])
 def test_pixel_centres_reproduce_map2alm(s):
     """A HEALPix map is a set of points of weight 4 pi / npix: the HEALPix route and the point transform must agree."""
     import heracles_amd as hx
@@ -168,6 +167,19 @@ def test_alm2map_against_direct_sum(nside, lmax, s):
     assert err < TOL
 
 
+@pytest.mark.parametrize("nside,lmax", [(8, 20), (32, 48), (128, 200)])
+@pytest.mark.parametrize("s", [4, 5, 8])
+def test_alm2map_higher_weights_against_direct_sum(nside, lmax, s):
+    import heracles_amd as hx
+
+    alm, pix, want = _synthesis_case(nside, lmax, s)
+    got = hx.get_plan(nside, lmax).alm2map(alm, s)
+    assert got.shape == (2, 12 * nside * nside) and np.abs(want).max() > 0
+    err = np.abs(got[:, pix] - want).max() / np.abs(want).max()
+    print(f"nside {nside} lmax {lmax} s {s}: err {err:.3e} at {pix.size} pixels")
+    assert err < TOL
+
+
 # ---- 5. adjointness ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nside,lmax", [(16, 24), (64, 100)])
 def test_adjointness(nside, lmax):
@@ -185,7 +197,7 @@ def test_adjointness(nside, lmax):
 
     npix = 12 * nside * nside
     plan = hx.get_plan(nside, lmax)
-    for s in (2, 1, 3):
+    for s in (2, 1, 3, 4, 5):
         rng = np.random.default_rng(5 * nside + s)
         maps = rng.standard_normal((2, npix))
         alm2 = helpers.random_alm(rng, lmax, s, (2,))
@@ -222,6 +234,56 @@ def test_spin2_through_the_general_sweeps(nside, lmax, monkeypatch):
     assert _err(m_gen, m_before) < 1e-12
     assert np.abs(a_gen - a_before).max() > 0.0 and np.abs(m_gen - m_before).max() > 0.0  # (the hook did take the other kernels)
     assert np.array_equal(a_after, a_before) and np.array_equal(m_after, m_before)
+
+
+# ---- 6b. the run-time-spin sweep in m-chunks --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("s", [1, 3])
+def test_map2alm_m_chunked(s):
+    """tests/test_gpu_sht.py's test_map2alm_m_chunked_batches_medium for the run-time-spin sweep: nside 256 / lmax 511 with the scratch
+    budget lowered through hx_set_scratch_budget, so that the sweep is cut into m-chunks [m0, m1) whose rows of partial sums start at
+    rows_before_m[m0] != 0, without and with one Jacobi iteration (whose second analysis ADDS into the alms: add = 1 in
+    k_alm_reduce_spin).  The chunking must not change a bit, and the chunked alms are the direct sum of the map (at most 400 non-zero
+    pixels, resident on the device) on every 16th m."""
+    import torch
+    import heracles_amd as hx
+
+    nside, lmax = 256, 511
+    npix = 12 * nside * nside
+    rng = np.random.default_rng(2560 + s)
+    pix = _special_pixels(nside, rng)
+    vals = rng.standard_normal((2, pix.size))
+    assert 0 < pix.size <= 400
+    dev = torch.zeros((2, npix), dtype=torch.float64, device="cuda")
+    dev[:, torch.as_tensor(pix).cuda()] = torch.as_tensor(vals).cuda()
+    plan = hx.get_plan(nside, lmax)
+    whole = plan.map2alm(dev, s).cpu().numpy()
+    assert plan.last_chunks == 1
+    whole1 = plan.map2alm(dev, s, niter=1).cpu().numpy()
+    assert plan.last_chunks == 1
+    hx._lib.set_scratch_budget(2.0e6)
+    try:
+        out = plan.map2alm(dev, s).cpu().numpy()
+        nchunks = plan.last_chunks
+        out1 = plan.map2alm(dev, s, niter=1).cpu().numpy()
+        nchunks1 = plan.last_chunks
+    finally:
+        hx._lib.set_scratch_budget(0)
+    print(f"nside {nside} lmax {lmax} s {s}: {nchunks} m-chunks, {nchunks1} with niter 1")
+    assert nchunks >= 3 and nchunks1 >= 3, (nchunks, nchunks1)
+    np.testing.assert_array_equal(out, whole)  # the chunking does not change a bit
+    np.testing.assert_array_equal(out1, whole1)
+    assert np.abs(out1 - out).max() > 0  # (the iteration did add something)
+    orders = range(0, lmax + 1, 16)
+    theta, phi = oracle.pix2ang(nside)
+    want = points2alm_spin(theta[pix], phi[pix], vals * (4 * np.pi / npix), lmax, s, orders=orders)
+    scale = np.abs(want).max()
+    worst = 0.0
+    for m in orders:
+        lo = helpers.idx(lmax, m, m)
+        worst = max(worst, np.abs(out[:, lo : lo + lmax - m + 1] - want[:, lo : lo + lmax - m + 1]).max())
+    print(f"nside {nside} lmax {lmax} s {s}: err {worst / scale:.3e} on every 16th m")
+    assert worst < TOL * scale
+    assert _low_rows_are_zero(out, lmax, s) and _low_rows_are_zero(out1, lmax, s)
 
 
 # ---- 7. iterations, weights, filter -----------------------------------------------------------------------------------------------

@@ -56,6 +56,23 @@ def test_random_points_against_direct_sum(lmax, s):
         assert not got[:, i : i + s - m].any()
 
 
+# weights with more than three orders m < s (the m < s seeds, chains from l0 = s > m, off = (l0 + m) & 1 on both parities), even
+# and odd; 8 with s = 8: s = lmax, one row per order
+@pytest.mark.parametrize("lmax", [8, 31, 100])
+@pytest.mark.parametrize("s", [4, 5, 8])
+def test_higher_weights_against_direct_sum(lmax, s):
+    import heracles_amd as hx
+
+    theta, phi, v, want = _case(lmax, s, 500)
+    got = hx.PointSHT(lmax).adjoint_synthesis(np.stack([theta, phi], axis=1), v, spin=s)
+    assert got.shape == want.shape and np.abs(want).max() > 0
+    print(f"lmax {lmax} s {s}: err {_err(got, want):.3e}")
+    assert _err(got, want) < 1e-11
+    for m in range(s):  # rows l < s are exact zeros
+        i = helpers.idx(lmax, m, m)
+        assert not got[:, i : i + s - m].any()
+
+
 @pytest.mark.parametrize("s", [1, 3])
 def test_lmax_300_all_m(s):
     """Ring pruning by ring_mlim(lmax, s) and the scaled seeds are live: sin^m(theta) underflows on the polar rings."""
@@ -68,7 +85,7 @@ def test_lmax_300_all_m(s):
     assert _err(got, want) < 1e-11
 
 
-@pytest.mark.parametrize("s", [1, 3])
+@pytest.mark.parametrize("s", [1, 3, 4, 5])
 def test_poles_seam_and_longitude_range(s):
     import heracles_amd as hx
 
@@ -91,6 +108,63 @@ def test_poles_seam_and_longitude_range(s):
     others[lo : lo + lmax - s + 1] = False
     assert not want[:, others].any() and np.abs(want).max() > 0.1
     assert _err(got, want) < 1e-11
+
+
+_LONG_CASES = {}
+_LONG_STRIDE = 300
+
+
+def _long_case(lmax, s):
+    """The point sets of tests/test_gpu_pointsht.py's test_long_transforms_on_sampled_m (40 points away from the poles; the same with
+    three of them at 1e-4, pi - 3e-4 and pi / 2) and their direct-sum alms on every 300th m: computed once per (lmax, s), shared
+    by the two spreading paths, never written."""
+    if (lmax, s) not in _LONG_CASES:
+        rng = np.random.default_rng(10 * lmax + s)
+        n = 40
+        theta = np.arccos(rng.uniform(-0.995, 0.995, n))
+        phi = rng.uniform(0, 2 * np.pi, n)
+        v = rng.normal(size=(2, n))
+        polar = theta.copy()
+        polar[:3] = [1e-4, np.pi - 3e-4, np.pi / 2]
+        wants = [points2alm_spin(t, phi, v, lmax, s, orders=range(0, lmax + 1, _LONG_STRIDE)) for t in (theta, polar)]
+        for a in (theta, polar, phi, v, *wants):
+            a.setflags(write=False)
+        _LONG_CASES[lmax, s] = (phi, v, (theta, wants[0]), (polar, wants[1]))
+    return _LONG_CASES[lmax, s]
+
+
+@pytest.mark.parametrize("tiles", [False, True])  # the default spreading path, and the LDS tiles (HX_NUFFT_TILES=1, read on every call)
+@pytest.mark.parametrize("lmax", [2100, 4200])  # FFT lengths 16384 and 32768
+@pytest.mark.parametrize("s", [1, 3])
+def test_long_transforms_on_sampled_m(s, lmax, tiles, monkeypatch):
+    """tests/test_gpu_pointsht.py's test of the same name for the run-time-spin sweep, with its bounds and their reasons: 1e-11 away
+    from the poles; for the set with points within a few rings of a pole 10 * lmax * 1.1e-16 / sin(first ring), the conditioning of
+    a three-term recursion through x = cos(theta) in float64 (the direct sum runs in extended precision)."""
+    import heracles_amd as hx
+
+    if tiles:
+        monkeypatch.setenv("HX_NUFFT_TILES", "1")
+    else:
+        monkeypatch.delenv("HX_NUFFT_TILES", raising=False)
+    sht = hx.PointSHT(lmax)
+    phi, v, away, polar = _long_case(lmax, s)
+
+    def worst_error(theta, want):
+        got = sht.adjoint_synthesis(np.stack([theta, phi], axis=1), v, spin=s)
+        worst = 0.0
+        for m in range(0, lmax + 1, _LONG_STRIDE):
+            lo = helpers.idx(lmax, m, m)
+            hi = lo + lmax - m + 1
+            worst = max(worst, np.abs(got[:, lo:hi] - want[:, lo:hi]).max())
+            if m < s:
+                assert not got[:, lo : lo + s - m].any()
+        return worst / np.abs(want).max()
+
+    e_away, e_polar = worst_error(*away), worst_error(*polar)
+    bound = 10 * lmax * 1.1e-16 / np.sin(np.pi / sht.nrings_circle)
+    print(f"lmax {lmax} s {s} tiles {tiles}: away {e_away:.3e} (1e-11), polar {e_polar:.3e} ({bound:.3e})")
+    assert e_away < 1e-11
+    assert e_polar < bound
 
 
 @pytest.mark.parametrize("lmax", [100, 300])
