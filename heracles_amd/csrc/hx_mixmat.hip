@@ -5,11 +5,17 @@
 // evaluated in its dense quadrature form:
 //   xi(x) = sum_{l3} (2 l3 + 1)/(4 pi) W_{l3} P_{l3}(x)
 //   G^{(ab)} = D^{(ab)T} diag(w xi) D^{(ab)} diag((2 l2 + 1)/2),   D^{(ab)}[k][l] = d^l_{ab}(x_k)
-// on N >= (l1max + l2max + l3max)/2 + 1 Gauss-Legendre nodes, which is exact.  The
+// on N >= (l1max + l2max + l3max)/2 + 1 Gauss-Legendre nodes, which is exact.  Fields of any spin weights (s1, s2) are served, and
+// their matrices are DEFINED by the quadrature form: G^{(s1,s2)} is (-1)^{s1+s2} times the product of 3j symbols above, so for odd
+// s1 + s2 the bare formula gives minus the identity for a full-sky mask and the quadrature form the identity (pseudo-Cl = M Cl).  The
 // (l, l') contraction is a symmetric FP64 GEMM on v_mfma_f64_16x16x4_f64; this is the only
 // place in the engine that is GEMM-shaped, so the only place MFMA is used as a GEMM.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <vector>
 
 #include "hx_common.h"
 
@@ -116,10 +122,38 @@ __device__ __forceinline__ DD dd_neg(DD a) { return DD{-a.h, -a.l}; }
 struct WigCoefDD {
     double c1xh, c1xl, c1ch, c1cl, c2h, c2l;
 };
+// sqrt of a positive double-double: one Newton step on the square root of the high part (r + (q - r^2) / (2 r), r^2 formed exactly)
+__device__ __forceinline__ DD dd_sqrt(DD q)
+{
+#pragma clang fp contract(off)
+    if (!(q.h > 0.0)) return DD{0.0, 0.0};
+    const double r = sqrt(q.h), rr = r * r, re = fma(r, r, -rr);
+    const double diff = ((q.h - rr) - re) + q.l;
+    return dd_quick(r, diff / (2.0 * r));
+}
+// The seed d^{l0}_{ab} of the recursion for any (a, b), from the host (wigner_seed): with (A, B) the pair brought to A >= |B| by
+// d_{ab} = (-1)^{a-b} d_{ba} = d_{-b,-a} and sg the sign that took it there,
+//   d^A_{AB}(x) = sqrt((2A)! / ((A+B)! (A-B)!)) ((1+x)/2)^{(A+B)/2} ((1-x)/2)^{(A-B)/2},
+// pp = A + B, pm = A - B (both even or both odd), c = the square root of the binomial as (hi, lo).
+struct WigSeed {
+    int pp, pm;
+    double ch, cl, sg;
+    int general;  // 1: take the general seed also for the pairs that have a branch of their own (test hook)
+};
+__device__ __forceinline__ DD wigner_seed_dd(const WigSeed sd, DD op, DD om)
+{
+    const DD hp = DD{0.5 * op.h, 0.5 * op.l}, hm = DD{0.5 * om.h, 0.5 * om.l};
+    DD v = DD{1.0, 0.0};
+    for (int i = 0; i < sd.pp / 2; ++i) v = dd_mul(v, hp);
+    for (int i = 0; i < sd.pm / 2; ++i) v = dd_mul(v, hm);
+    if (sd.pp & 1) v = dd_mul(v, dd_sqrt(dd_mul(hp, hm)));  // (pp and pm are odd together: one factor sqrt((1 - x^2) / 4))
+    v = dd_mul(DD{sd.ch, sd.cl}, v);
+    return DD{sd.sg * v.h, sd.sg * v.l};
+}
 // out[l * sl + k * sk] = d^l_{ab}(x_k + xlo_k), l = 0..lmax; s6: sqrt(6) / 4 as (hi, lo)
 __global__ void k_wigner_table_dd(int lmax, int a, int b, int n, const double *__restrict__ x, const double *__restrict__ xlo,
                                   const WigCoefDD *__restrict__ coef, double *__restrict__ out, long long sl, long long sk, double s6h,
-                                  double s6l)
+                                  double s6l, WigSeed sd)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -128,12 +162,14 @@ __global__ void k_wigner_table_dd(int lmax, int a, int b, int n, const double *_
     const DD om = dd_add(one, dd_neg(xx)), op = dd_add(one, xx);
     const int l0 = max(abs(a), abs(b));
     DD d0;
-    if (a == 0 && b == 0) d0 = one;
+    if (sd.general) d0 = wigner_seed_dd(sd, op, om);
+    else if (a == 0 && b == 0) d0 = one;
     else if (a == 2 && b == 0) d0 = dd_mul(DD{s6h, s6l}, dd_mul(om, op));
     else if (a == 2 && b == 2) { d0 = dd_mul(op, op); d0.h *= 0.25; d0.l *= 0.25; }
     else if (a == 1 && b == 1) { d0 = op; d0.h *= 0.5; d0.l *= 0.5; }     // d^1_{11}   (heracles/transforms.py:68-73)
     else if (a * b == -1) { d0 = om; d0.h *= 0.5; d0.l *= 0.5; }          // d^1_{-1,1} = d^1_{1,-1}
-    else { d0 = dd_mul(om, om); d0.h *= 0.25; d0.l *= 0.25; }  // (2,-2)
+    else if (a == 2 && b == -2) { d0 = dd_mul(om, om); d0.h *= 0.25; d0.l *= 0.25; }
+    else d0 = wigner_seed_dd(sd, op, om);
     for (int l = 0; l < l0 && l <= lmax; ++l) out[l * sl + k * sk] = 0.0;
     if (l0 > lmax) return;
     DD dp = DD{0.0, 0.0}, dc = d0;
@@ -635,6 +671,50 @@ static void wigner_coefs_dd(int lmax, int a, int b, std::vector<WigCoefDD> &c)
     }
 }
 
+// (a, b) brought to A >= |B|, A >= 0 by d_{ab} = (-1)^{a-b} d_{ba} = d_{-b,-a}; returns the sign that took it there
+static double wigner_normal_pair(int a, int b, int &A, int &B)
+{
+    const double flip = ((a - b) & 1) ? -1.0 : 1.0;
+    if (abs(a) >= abs(b)) {
+        if (a >= 0) { A = a; B = b; return 1.0; }
+        A = -a; B = -b;
+        return flip;
+    }
+    if (b > 0) { A = b; B = a; return flip; }
+    A = -b; B = -a;
+    return 1.0;
+}
+// the seed of k_wigner_table_dd for any (a, b), max(|a|, |b|) <= HX_MAX_MIX_SPIN: the binomial (2A over A+B) <= (64 over 32) < 2^63 is
+// formed in integers, its root in the host's long double and handed over as (hi, lo), like sqrt(6) / 4 of the (2,0) branch
+static WigSeed wigner_seed(int a, int b)
+{
+    WigSeed sd;
+    int A, B;
+    sd.sg = wigner_normal_pair(a, b, A, B);
+    sd.pp = A + B;
+    sd.pm = A - B;
+    unsigned __int128 bin = 1;
+    for (int i = 1; i <= sd.pm; ++i) bin = bin * (unsigned)(sd.pp + i) / (unsigned)i;
+    const long double c = sqrtl((long double)(unsigned long long)bin);
+    sd.ch = (double)c;
+    sd.cl = (double)(c - (long double)sd.ch);
+    const char *e = getenv("HX_WIGNER_SEED");
+    sd.general = e && !strcmp(e, "general");
+    return sd;
+}
+// out[l * sl + k * sk] = d^l_{ab}(x_k + xlo_k), l = 0 .. lmax, on the stream of the library
+static int launch_wigner_table(int lmax, int a, int b, int n, const double *d_x, const double *d_xlo, const WigCoefDD *d_coef, double *d_out,
+                               long long sl, long long sk)
+{
+    ProfScope ps("wigner_tables");
+    const long double s6 = sqrtl(6.0L) / 4.0L;
+    const double s6h = (double)s6, s6l = (double)(s6 - (long double)s6h);
+    hipLaunchKernelGGL(k_wigner_table_dd, dim3((n + 63) / 64), dim3(64), 0, rt().stream, lmax, a, b, n, d_x, d_xlo, d_coef, d_out, sl, sk, s6h, s6l,
+                       wigner_seed(a, b));
+    HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
 int launch_gauss_legendre(int n, double *d_x, double *d_w, double *d_xlo)
 {
     const int half = (n + 1) / 2;
@@ -671,21 +751,32 @@ static int gl_nodes_device(int n, GLCache &c)
 // T_ab[l][k] = d^l_ab(x_k) of the products asked for, the tile list and the column scaling (2 l2 + 1) / 2.  One context
 // serves any number of masks: per mask only the node weights s_k = w_k xi(x_k) and one GEMM per product remain
 // (the reference calls convolvecl once per (field pair, bin pair), heracles/twopoint.py:354-397, rebuilding all of it).
+struct MixTable {
+    int a = 0, b = 0;
+    DevBuf T, Tb;  // the table [rows_pad][kpad] and its binned rows [nbpad][kpad] (hx_mixctx_set_bins)
+    bool have = false, have_b = false;
+    unsigned long long used = 0;
+};
 struct MixCtx {
     int l1max = -1, l2max = -1, l3max = -1, L = 0, n = 0, kpad = 0, rows_pad = 0;
     GLCache gl;
     DevBuf s, d_tiles, d_cs;
     size_t ntiles = 0;
-    DevBuf T[4];            // (0,0), (2,0), (2,2), (2,-2)
+    // Tables by normalised pair (a >= |b|: G^{(ab)} is the same for (a, b), (b, a) and (-b, -a), see wigner_normal_pair).  (0,0) has a
+    // place of its own and is never dropped: the node weights of every mask read it.  Of the others at most max_tabs are kept
+    // (HX_MIX_TABLES at creation; 16 holds every pair of a job with spins {0, 1, 2, 3}: three (s, 0) and twelve (s1, +-s2)), the one
+    // used longest ago goes first.  A table is rows_pad x kpad doubles: 0.46 GB at L = 6144.
+    MixTable t0;
+    std::vector<std::unique_ptr<MixTable>> tabs;
+    int max_tabs = 16;
+    unsigned long long tick = 0;
     DevBuf Ts;              // T diag(s) of the product in hand (k_mixmat_gemm_dma)
     DevBuf xi_part;         // slices of the node weights of the mask in hand (k_xi_partial)
-    int rows0_pad = 0;      // rows of T[0]: it also serves the node weights, whose sum runs to l3max
-    bool have[4] = {false, false, false, false};
+    int rows0_pad = 0;      // rows of t0: it also serves the node weights, whose sum runs to l3max
     // binned rows (hx_mixctx_set_bins): bin lists of the output multipole, binned tables Tb_t[nbpad][kpad] per product
     int nbins = 0, nbpad = 0, l2pad = 0, ksplit = 1, kchunk = 0;
     DevBuf b_start, b_rows, b_w, b_norm;
-    DevBuf Tb[4], Tbs, part[2], b_out;  // (b_out: device image of a host destination, kept between calls)
-    bool have_b[4] = {false, false, false, false};
+    DevBuf Tbs, part[2], b_out;  // (b_out: device image of a host destination, kept between calls)
     // page-locked landing buffer of a binned result on its way to a pageable destination (the GPU writes it by DMA; the bytes are then
     // copied on by the host): straight into a fresh numpy array, the runtime pins the caller's pages call by call -- 3 ms per 1.5 MB key in
     // a process that holds a plan's scratch, against 0.15 ms this way (tools/exp_mixmat_list_env.py)
@@ -699,8 +790,6 @@ struct MixCtx {
         if (b_pin) (void)hipHostFree(b_pin);
     }
 };
-static const int kAB[4][2] = {{0, 0}, {2, 0}, {2, 2}, {2, -2}};
-
 static int mix_ctx_init(MixCtx &c, int l1max, int l2max, int l3max)
 {
     hipStream_t st = rt().stream;
@@ -709,6 +798,7 @@ static int mix_ctx_init(MixCtx &c, int l1max, int l2max, int l3max)
     c.n = (l1max + l2max + l3max) / 2 + 1;
     c.kpad = (c.n + GK - 1) / GK * GK;
     c.rows_pad = (c.L + 1 + GB - 1) / GB * GB;
+    if (const char *e = getenv("HX_MIX_TABLES")) c.max_tabs = std::max(1, atoi(e));
     HX_TRY(gl_nodes_device(c.n, c.gl));
     HX_TRY(c.s.alloc(sizeof(double) * c.kpad));
     // Tile order: work-groups go to the 8 XCDs round-robin (blockIdx % 8), and an XCD runs 64 of them at a time (32 CUs x 2).  The
@@ -747,29 +837,46 @@ static int mix_ctx_init(MixCtx &c, int l1max, int l2max, int l3max)
     return HX_OK;
 }
 
-static int mix_ctx_table(MixCtx &c, int t)
+// the table of the pair (a, b), built on first use; *out stays valid until the next call of this function
+static int mix_ctx_table(MixCtx &c, int a, int b, MixTable **out)
 {
-    if (c.have[t]) return HX_OK;
+    int A, B;
+    (void)wigner_normal_pair(a, b, A, B);
+    if (A > HX_MAX_MIX_SPIN) return fail(HX_ERR_UNSUPPORTED, "mixmat: spin %d beyond the supported %d", A, HX_MAX_MIX_SPIN);
     hipStream_t st = rt().stream;
+    const bool zero = A == 0;
+    MixTable *t = zero ? &c.t0 : nullptr;
+    for (size_t i = 0; !t && i < c.tabs.size(); ++i)
+        if (c.tabs[i]->a == A && c.tabs[i]->b == B) t = c.tabs[i].get();
+    if (!t) {
+        if ((int)c.tabs.size() >= c.max_tabs) {
+            size_t old = 0;
+            for (size_t i = 1; i < c.tabs.size(); ++i)
+                if (c.tabs[i]->used < c.tabs[old]->used) old = i;
+            HX_HIP(hipStreamSynchronize(st));  // (a product may still be reading it)
+            c.tabs.erase(c.tabs.begin() + old);
+        }
+        c.tabs.emplace_back(new MixTable);
+        t = c.tabs.back().get();
+        t->a = A;
+        t->b = B;
+    }
+    t->used = ++c.tick;
+    *out = t;
+    if (t->have) return HX_OK;
     // (the (0,0) table = P_l(x_k) also feeds the node weights xi(x_k) of every mask, a sum over l <= l3max: its rows run that far)
-    const int ltop = t == 0 ? std::max(c.L, c.l3max) : c.L;
-    const int rows = t == 0 ? (ltop + 1 + GB - 1) / GB * GB : c.rows_pad;
-    if (t == 0) c.rows0_pad = rows;
+    const int ltop = zero ? std::max(c.L, c.l3max) : c.L;
+    const int rows = zero ? (ltop + 1 + GB - 1) / GB * GB : c.rows_pad;
+    if (zero) c.rows0_pad = rows;
     std::vector<WigCoefDD> coef;
-    wigner_coefs_dd(ltop, kAB[t][0], kAB[t][1], coef);
+    wigner_coefs_dd(ltop, A, B, coef);
     DevBuf d_coef;
     HX_TRY(upload_vec(d_coef, coef));
-    HX_TRY(c.T[t].alloc(sizeof(double) * (size_t)rows * c.kpad));
-    HX_HIP(hipMemsetAsync(c.T[t].p, 0, sizeof(double) * (size_t)rows * c.kpad, st));
-    {
-        ProfScope ps("wigner_tables");
-        const long double s6 = sqrtl(6.0L) / 4.0L;
-        const double s6h = (double)s6, s6l = (double)(s6 - (long double)s6h);
-        hipLaunchKernelGGL(k_wigner_table_dd, dim3((c.n + 63) / 64), dim3(64), 0, st, ltop, kAB[t][0], kAB[t][1], c.n, c.gl.x.as<double>(),
-                           c.gl.xlo.as<double>(), d_coef.as<WigCoefDD>(), c.T[t].as<double>(), (long long)c.kpad, 1LL, s6h, s6l);
-    }
+    HX_TRY(t->T.alloc(sizeof(double) * (size_t)rows * c.kpad));
+    HX_HIP(hipMemsetAsync(t->T.p, 0, sizeof(double) * (size_t)rows * c.kpad, st));
+    HX_TRY(launch_wigner_table(ltop, A, B, c.n, c.gl.x.as<double>(), c.gl.xlo.as<double>(), d_coef.as<WigCoefDD>(), t->T.as<double>(), (long long)c.kpad, 1LL));
     HX_HIP(hipStreamSynchronize(st));  // d_coef dies with this scope
-    c.have[t] = true;
+    t->have = true;
     return HX_OK;
 }
 
@@ -777,27 +884,29 @@ static int mix_ctx_table(MixCtx &c, int t)
 static int mix_ctx_mask(MixCtx &c, const double *d_cl)
 {
     hipStream_t st = rt().stream;
-    HX_TRY(mix_ctx_table(c, 0));
+    MixTable *t0 = nullptr;
+    HX_TRY(mix_ctx_table(c, 0, 0, &t0));
     HX_TRY(c.xi_part.alloc(sizeof(double2) * (size_t)XI_SLICES * c.kpad));
     HX_HIP(hipMemsetAsync(c.s.p, 0, sizeof(double) * c.kpad, st));
     ProfScope ps("weight_xi");
-    hipLaunchKernelGGL(k_xi_partial, dim3((c.kpad + 63) / 64, XI_SLICES), dim3(256), 0, st, c.l3max, c.kpad, d_cl, c.T[0].as<double>(), c.xi_part.as<double2>());
+    hipLaunchKernelGGL(k_xi_partial, dim3((c.kpad + 63) / 64, XI_SLICES), dim3(256), 0, st, c.l3max, c.kpad, d_cl, t0->T.as<double>(), c.xi_part.as<double2>());
     hipLaunchKernelGGL(k_xi_finish, dim3((c.n + 255) / 256), dim3(256), 0, st, c.n, c.kpad, c.gl.w.as<double>(), c.xi_part.as<double2>(), c.s.as<double>());
     HX_HIP(hipGetLastError());
     return HX_OK;
 }
 
 // G^{(ab)} of the current mask into d_out (device, (l1max + 1) x (l2max + 1), ld = l2max + 1)
-static int mix_ctx_product(MixCtx &c, int t, double *d_out)
+static int mix_ctx_product(MixCtx &c, int a, int b, double *d_out)
 {
-    HX_TRY(mix_ctx_table(c, t));
+    MixTable *t = nullptr;
+    HX_TRY(mix_ctx_table(c, a, b, &t));
     ProfScope ps("mixmat_gemm");
     const size_t nel = (size_t)c.rows_pad * c.kpad;
     if (!c.Ts.p) HX_TRY(c.Ts.alloc(sizeof(double) * nel));
-    hipLaunchKernelGGL(k_scale_table, dim3(2048), dim3(256), 0, rt().stream, (long long)(nel / 2), c.kpad / 2, c.T[t].as<double2>(), c.s.as<double2>(),
+    hipLaunchKernelGGL(k_scale_table, dim3(2048), dim3(256), 0, rt().stream, (long long)(nel / 2), c.kpad / 2, t->T.as<double2>(), c.s.as<double2>(),
                        c.Ts.as<double2>());
     ProfScope pk("mixmat_gemm_kernel");  // (the matrix kernel alone; "mixmat_gemm" includes the scaling pass)
-    hipLaunchKernelGGL(k_mixmat_gemm_dma<true>, dim3((unsigned)c.ntiles), dim3(256), 0, rt().stream, c.Ts.as<double>(), c.T[t].as<double>(), c.kpad,
+    hipLaunchKernelGGL(k_mixmat_gemm_dma<true>, dim3((unsigned)c.ntiles), dim3(256), 0, rt().stream, c.Ts.as<double>(), t->T.as<double>(), c.kpad,
                        c.d_tiles.as<int2>(), c.l1max + 1, c.l2max + 1, c.d_cs.as<double>(), d_out, (long long)(c.l2max + 1));
     HX_HIP(hipGetLastError());
     return HX_OK;
@@ -881,16 +990,17 @@ static int mix_bind_out(OutView &vo, double *out, size_t bytes)
     vo.host = out;
     return HX_OK;
 }
-// The three spin-2 x spin-2 matrices of one mask (context c, node weights set) into vo = [3][n1][n2].
-// b = G^{(2,-2)} first: it IS the third matrix, so a host destination receives it (second stream, ~5 ms at L = 6144) while the
-// product a = G^{(2,2)} is computed; then [0] = (a + b) / 2, [1] = (a - b) / 2.  Complete on return for a host destination.
-static int mix_eb_into(MixCtx &c, OutView &vo)
+// The three matrices of two fields of non-zero spin weights s1, s2 > 0 for one mask (context c, node weights set) into vo = [3][n1][n2].
+// b = G^{(s1,-s2)} first: it IS the third matrix, so a host destination receives it (second stream, ~5 ms at L = 6144) while the
+// product a = G^{(s1,s2)} is computed; then [0] = (a + b) / 2, [1] = (a - b) / 2.  Complete on return for a host destination.
+static int mix_eb_into(MixCtx &c, OutView &vo, int s1, int s2)
 {
     const size_t sz = (size_t)(c.l1max + 1) * (c.l2max + 1);
     double *o0 = vo.as<double>(), *o1 = o0 + sz, *o2 = o0 + 2 * sz;
     hipStream_t st = rt().stream;
-    HX_TRY(mix_ctx_product(c, 3, o2));
-    HX_TRY(mix_ctx_table(c, 2));
+    MixTable *ta = nullptr;
+    HX_TRY(mix_ctx_product(c, s1, -s2, o2));
+    HX_TRY(mix_ctx_table(c, s1, s2, &ta));
     hipStream_t cs = vo.host ? copy_stream() : nullptr;
     if (cs) {
         Runtime &r = rt();
@@ -898,7 +1008,7 @@ static int mix_eb_into(MixCtx &c, OutView &vo)
         HX_HIP(hipEventRecord(r.order_ev, st));
         HX_HIP(hipStreamWaitEvent(cs, r.order_ev, 0));
     }
-    HX_TRY(mix_ctx_product(c, 2, o0));
+    HX_TRY(mix_ctx_product(c, s1, s2, o0));
     if (cs) HX_TRY(copy_d2h((double *)vo.host + 2 * sz, o2, sizeof(double) * sz, cs));  // (complete on return; the product above runs meanwhile)
     hipLaunchKernelGGL(k_eb_combine, dim3(1024), dim3(256), 0, st, (long long)sz, o0, o1, o2);
     HX_HIP(hipGetLastError());
@@ -956,8 +1066,8 @@ extern "C" int hx_wigner_d_table(int lmax, int a, int b, int n, const double *x,
 {
     HX_TRY(ensure_ready());
     if (lmax < 0 || n < 1 || !x || !out) return fail(HX_ERR_ARG, "hx_wigner_d_table: bad argument");
-    if (!((a == 0 && b == 0) || (a == 2 && b == 0) || (a == 2 && b == 2) || (a == 2 && b == -2) || (a == 1 && b == 1) || (a * b == -1)))
-        return fail(HX_ERR_UNSUPPORTED, "hx_wigner_d_table: (a,b)=(%d,%d) not supported", a, b);
+    if (std::max(abs(a), abs(b)) > HX_MAX_MIX_SPIN)
+        return fail(HX_ERR_UNSUPPORTED, "hx_wigner_d_table: (a,b)=(%d,%d) beyond the supported max(|a|,|b|) <= %d", a, b, HX_MAX_MIX_SPIN);
     InView vx;
     OutView vo;
     HX_TRY(vx.bind(x, sizeof(double) * n));
@@ -969,14 +1079,7 @@ extern "C" int hx_wigner_d_table(int lmax, int a, int b, int n, const double *x,
     HX_TRY(upload_vec(d_coef, coef));
     HX_TRY(d_zero.alloc(sizeof(double) * n));
     HX_HIP(hipMemsetAsync(d_zero.p, 0, sizeof(double) * n, rt().stream));
-    {
-        ProfScope ps("wigner_tables");
-        const long double s6 = sqrtl(6.0L) / 4.0L;
-        const double s6h = (double)s6, s6l = (double)(s6 - (long double)s6h);
-        hipLaunchKernelGGL(k_wigner_table_dd, dim3((n + 63) / 64), dim3(64), 0, rt().stream, lmax, a, b, n, vx.as<double>(), d_zero.as<double>(),
-                           d_coef.as<WigCoefDD>(), vo.as<double>(), 1LL, (long long)(lmax + 1), s6h, s6l);
-    }
-    HX_HIP(hipGetLastError());
+    HX_TRY(launch_wigner_table(lmax, a, b, n, vx.as<double>(), d_zero.as<double>(), d_coef.as<WigCoefDD>(), vo.as<double>(), 1LL, (long long)(lmax + 1)));
     HX_TRY(vo.finish());
     HX_HIP(hipStreamSynchronize(rt().stream));
     return HX_OK;
@@ -993,10 +1096,9 @@ extern "C" int hx_mixmat(const double *cl, int ncl, int l1max, int l2max, int l3
 {
     HX_TRY(ensure_ready());
     HX_TRY(mixmat_args(cl, ncl, l1max, l2max, l3max, out));
-    int ab[1][2];
-    if (s1 == 0 && s2 == 0) { ab[0][0] = 0; ab[0][1] = 0; }
-    else if ((abs(s1) == 2 && s2 == 0) || (s1 == 0 && abs(s2) == 2)) { ab[0][0] = 2; ab[0][1] = 0; }
-    else return fail(HX_ERR_UNSUPPORTED, "hx_mixmat: spin (%d,%d) not supported (use hx_mixmat_eb for (2,2))", s1, s2);
+    if (s1 != 0 && s2 != 0) return fail(HX_ERR_UNSUPPORTED, "hx_mixmat: spin (%d,%d) not supported (use hx_mixmat_eb_spin for two non-zero spins)", s1, s2);
+    const int s = std::max(abs(s1), abs(s2));
+    if (s > HX_MAX_MIX_SPIN) return fail(HX_ERR_UNSUPPORTED, "hx_mixmat: spin %d beyond the supported %d", s, HX_MAX_MIX_SPIN);
     MixCtx *c = nullptr;
     HX_TRY(mix_cached_ctx(l1max, l2max, l3max, &c));
     DevBuf &d_cl = mix_cache().cl;
@@ -1004,16 +1106,27 @@ extern "C" int hx_mixmat(const double *cl, int ncl, int l1max, int l2max, int l3
     OutView vo;
     HX_TRY(mix_bind_out(vo, out, sizeof(double) * (size_t)(l1max + 1) * (l2max + 1)));
     HX_TRY(mix_ctx_mask(*c, d_cl.as<double>()));
-    HX_TRY(mix_ctx_product(*c, ab[0][0] == 0 ? 0 : 1, vo.as<double>()));
+    HX_TRY(mix_ctx_product(*c, s, 0, vo.as<double>()));
     HX_TRY(vo.finish());
     HX_HIP(hipStreamSynchronize(rt().stream));
     return HX_OK;
 }
 
-extern "C" int hx_mixmat_eb(const double *cl, int ncl, int l1max, int l2max, int l3max, double *out)
+// spins by magnitude, both non-zero and <= HX_MAX_MIX_SPIN
+static int mix_two_spins(const char *who, int &s1, int &s2)
+{
+    s1 = abs(s1);
+    s2 = abs(s2);
+    if (s1 == 0 || s2 == 0) return fail(HX_ERR_UNSUPPORTED, "%s: spin (%d,%d): three matrices need two non-zero spins (hx_mixmat serves the others)", who, s1, s2);
+    if (std::max(s1, s2) > HX_MAX_MIX_SPIN) return fail(HX_ERR_UNSUPPORTED, "%s: spin %d beyond the supported %d", who, std::max(s1, s2), HX_MAX_MIX_SPIN);
+    return HX_OK;
+}
+
+extern "C" int hx_mixmat_eb_spin(const double *cl, int ncl, int l1max, int l2max, int l3max, int s1, int s2, double *out)
 {
     HX_TRY(ensure_ready());
     HX_TRY(mixmat_args(cl, ncl, l1max, l2max, l3max, out));
+    HX_TRY(mix_two_spins("hx_mixmat_eb_spin", s1, s2));
     const size_t sz = (size_t)(l1max + 1) * (l2max + 1);
     MixCtx *c = nullptr;
     HX_TRY(mix_cached_ctx(l1max, l2max, l3max, &c));
@@ -1022,9 +1135,14 @@ extern "C" int hx_mixmat_eb(const double *cl, int ncl, int l1max, int l2max, int
     OutView vo;
     HX_TRY(mix_bind_out(vo, out, sizeof(double) * 3 * sz));
     HX_TRY(mix_ctx_mask(*c, d_cl.as<double>()));
-    HX_TRY(mix_eb_into(*c, vo));
+    HX_TRY(mix_eb_into(*c, vo, s1, s2));
     HX_HIP(hipStreamSynchronize(rt().stream));
     return HX_OK;
+}
+
+extern "C" int hx_mixmat_eb(const double *cl, int ncl, int l1max, int l2max, int l3max, double *out)
+{
+    return hx_mixmat_eb_spin(cl, ncl, l1max, l2max, l3max, 2, 2, out);
 }
 
 // Shader clock in GHz under k_mixmat_gemm_dma since the last call (sampled tiles: shader ticks / 100 MHz ticks); 0 if none ran.
@@ -1137,21 +1255,21 @@ extern "C" int hx_mixmat_batch(int nmask, const double *cls, int ncl, int l1max,
         if (kinds[k] & 1) {
             OutView vo;
             HX_TRY(mix_bind_out(vo, out00[k], sizeof(double) * sz));
-            HX_TRY(mix_ctx_product(c, 0, vo.as<double>()));
+            HX_TRY(mix_ctx_product(c, 0, 0, vo.as<double>()));
             HX_TRY(vo.finish());
             HX_HIP(hipStreamSynchronize(rt().stream));
         }
         if (kinds[k] & 2) {
             OutView vo;
             HX_TRY(mix_bind_out(vo, out02[k], sizeof(double) * sz));
-            HX_TRY(mix_ctx_product(c, 1, vo.as<double>()));
+            HX_TRY(mix_ctx_product(c, 2, 0, vo.as<double>()));
             HX_TRY(vo.finish());
             HX_HIP(hipStreamSynchronize(rt().stream));
         }
         if (kinds[k] & 4) {
             OutView vo;
             HX_TRY(mix_bind_out(vo, outeb[k], sizeof(double) * 3 * sz));
-            HX_TRY(mix_eb_into(c, vo));
+            HX_TRY(mix_eb_into(c, vo, 2, 2));
             HX_HIP(hipStreamSynchronize(rt().stream));
         }
     }
@@ -1187,26 +1305,53 @@ extern "C" void hx_mixctx_destroy(hx_mixctx *x)
     delete x;
 }
 
-// kind 1: spin (0,0) -> out (l1max+1, l2max+1); 2: spin (0,2)/(2,0) -> the same shape; 4: spin (2,2) -> out (3, l1max+1, l2max+1)
-extern "C" int hx_mixctx_apply(hx_mixctx *x, const double *cl, int ncl, int kind, double *out)
+// the spins of a `kind` of hx_mixctx_apply / hx_mixctx_apply_binned: 1 -> (0,0), 2 -> (2,0), 4 -> (2,2)
+static bool mix_kind_spins(int kind, int &s1, int &s2)
+{
+    s1 = kind == 1 ? 0 : 2;
+    s2 = kind == 4 ? 2 : 0;
+    return kind == 1 || kind == 2 || kind == 4;
+}
+// spins by magnitude; both non-zero: three matrices (eb = true), else one
+static int mix_ctx_spins(const char *who, int &s1, int &s2, bool &eb)
+{
+    s1 = abs(s1);
+    s2 = abs(s2);
+    eb = s1 && s2;
+    if (std::max(s1, s2) > HX_MAX_MIX_SPIN) return fail(HX_ERR_UNSUPPORTED, "%s: spin %d beyond the supported %d", who, std::max(s1, s2), HX_MAX_MIX_SPIN);
+    return HX_OK;
+}
+
+// spins (s1, s2) by magnitude: one of them zero -> out (l1max+1, l2max+1); both non-zero -> out (3, l1max+1, l2max+1) as hx_mixmat_eb_spin
+extern "C" int hx_mixctx_apply_spin(hx_mixctx *x, const double *cl, int ncl, int s1, int s2, double *out)
 {
     HX_TRY(ensure_ready());
-    if (!x || !cl || !out || ncl < 1 || (kind != 1 && kind != 2 && kind != 4)) return fail(HX_ERR_ARG, "hx_mixctx_apply: bad argument");
+    if (!x || !cl || !out || ncl < 1) return fail(HX_ERR_ARG, "hx_mixctx_apply_spin: bad argument");
+    bool eb = false;
+    HX_TRY(mix_ctx_spins("hx_mixctx_apply_spin", s1, s2, eb));
     MixCtx &c = x->c;
     const size_t sz = (size_t)(c.l1max + 1) * (c.l2max + 1);
     DevBuf d_cl;
     HX_TRY(stage_cl(cl, ncl, c.l3max, d_cl));
     HX_TRY(mix_ctx_mask(c, d_cl.as<double>()));
     OutView vo;
-    HX_TRY(mix_bind_out(vo, out, sizeof(double) * sz * (kind == 4 ? 3 : 1)));  // (the staging buffer of a host destination is kept between calls)
-    if (kind == 4) {
-        HX_TRY(mix_eb_into(c, vo));
+    HX_TRY(mix_bind_out(vo, out, sizeof(double) * sz * (eb ? 3 : 1)));  // (the staging buffer of a host destination is kept between calls)
+    if (eb) {
+        HX_TRY(mix_eb_into(c, vo, s1, s2));
     } else {
-        HX_TRY(mix_ctx_product(c, kind == 1 ? 0 : 1, vo.as<double>()));
+        HX_TRY(mix_ctx_product(c, std::max(s1, s2), 0, vo.as<double>()));
         HX_TRY(vo.finish());
     }
     HX_HIP(hipStreamSynchronize(rt().stream));
     return HX_OK;
+}
+
+// kind 1: spin (0,0) -> out (l1max+1, l2max+1); 2: spin (0,2)/(2,0) -> the same shape; 4: spin (2,2) -> out (3, l1max+1, l2max+1)
+extern "C" int hx_mixctx_apply(hx_mixctx *x, const double *cl, int ncl, int kind, double *out)
+{
+    int s1, s2;
+    if (!mix_kind_spins(kind, s1, s2)) return fail(HX_ERR_ARG, "hx_mixctx_apply: bad argument");
+    return hx_mixctx_apply_spin(x, cl, ncl, s1, s2, out);
 }
 
 // ---- binned rows: heracles.twopoint.mixing_matrices(..., bins, weights) (heracles/twopoint.py:391-397) ----------------------------
@@ -1244,75 +1389,81 @@ extern "C" int hx_mixctx_set_bins(hx_mixctx *x, int nbins, const int *which, con
     HX_TRY(upload_vec(c.b_w, rw));
     std::vector<double> nv(norm, norm + nbins);
     HX_TRY(upload_vec(c.b_norm, nv));
-    for (bool &h : c.have_b) h = false;
+    c.t0.have_b = false;
+    for (auto &t : c.tabs) t->have_b = false;
     return HX_OK;
 }
 
 namespace hx {
-static int mix_ctx_binned_table(MixCtx &c, int t)
+static int mix_ctx_binned_table(MixCtx &c, int a, int b, MixTable **out)
 {
-    if (c.have_b[t]) return HX_OK;
-    HX_TRY(mix_ctx_table(c, t));
+    MixTable *t = nullptr;
+    HX_TRY(mix_ctx_table(c, a, b, &t));
+    *out = t;
+    if (t->have_b) return HX_OK;
     const size_t nel = (size_t)c.nbpad * c.kpad;
-    HX_TRY(c.Tb[t].alloc(sizeof(double) * nel));
-    HX_HIP(hipMemsetAsync(c.Tb[t].p, 0, sizeof(double) * nel, rt().stream));
+    HX_TRY(t->Tb.alloc(sizeof(double) * nel));
+    HX_HIP(hipMemsetAsync(t->Tb.p, 0, sizeof(double) * nel, rt().stream));
     ProfScope ps("mixmat_bin_table");
     hipLaunchKernelGGL(k_bin_table, dim3((c.kpad + 255) / 256, c.nbins), dim3(256), 0, rt().stream, c.kpad, c.b_start.as<int>(), c.b_rows.as<int>(),
-                       c.b_w.as<double>(), c.T[t].as<double>(), c.Tb[t].as<double>());
+                       c.b_w.as<double>(), t->T.as<double>(), t->Tb.as<double>());
     HX_HIP(hipGetLastError());
-    c.have_b[t] = true;
+    t->have_b = true;
     return HX_OK;
 }
 
-// shares of the numerators of product t for the current mask into c.part[slot]
-static int mix_ctx_binned_product(MixCtx &c, int t, int slot)
+// shares of the numerators of product (a, b) for the current mask into c.part[slot]
+static int mix_ctx_binned_product(MixCtx &c, int a, int b, int slot)
 {
-    HX_TRY(mix_ctx_binned_table(c, t));
+    MixTable *t = nullptr;
+    HX_TRY(mix_ctx_binned_table(c, a, b, &t));
     hipStream_t st = rt().stream;
     const size_t nel = (size_t)c.nbpad * c.kpad;
     HX_TRY(c.Tbs.alloc(sizeof(double) * nel));
     HX_TRY(c.part[slot].alloc(sizeof(double) * (size_t)c.ksplit * c.nbpad * c.l2pad));
     ProfScope ps("mixmat_binned");
-    hipLaunchKernelGGL(k_scale_table, dim3(256), dim3(256), 0, st, (long long)(nel / 2), c.kpad / 2, c.Tb[t].as<double2>(), c.s.as<double2>(), c.Tbs.as<double2>());
+    hipLaunchKernelGGL(k_scale_table, dim3(256), dim3(256), 0, st, (long long)(nel / 2), c.kpad / 2, t->Tb.as<double2>(), c.s.as<double2>(), c.Tbs.as<double2>());
     const int mt = std::min(c.nbpad / 16, 4);
     const dim3 grid(c.l2pad / 64, c.ksplit, c.nbpad / (16 * mt));
     if (mt == 1)
-        hipLaunchKernelGGL(k_binned_gemm<1>, grid, dim3(256), 0, st, c.Tbs.as<double>(), c.T[t].as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
+        hipLaunchKernelGGL(k_binned_gemm<1>, grid, dim3(256), 0, st, c.Tbs.as<double>(), t->T.as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
     else if (mt == 2)
-        hipLaunchKernelGGL(k_binned_gemm<2>, grid, dim3(256), 0, st, c.Tbs.as<double>(), c.T[t].as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
+        hipLaunchKernelGGL(k_binned_gemm<2>, grid, dim3(256), 0, st, c.Tbs.as<double>(), t->T.as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
     else
-        hipLaunchKernelGGL(k_binned_gemm<4>, grid, dim3(256), 0, st, c.Tbs.as<double>(), c.T[t].as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
+        hipLaunchKernelGGL(k_binned_gemm<4>, grid, dim3(256), 0, st, c.Tbs.as<double>(), t->T.as<double>(), c.kpad, c.kchunk, c.nbpad, c.l2pad, c.part[slot].as<double>());
     HX_HIP(hipGetLastError());
     return HX_OK;
 }
 }  // namespace hx
 
-// kind as hx_mixctx_apply; out (nbins, l2max + 1) or (3, nbins, l2max + 1), host or device: the rows of the matrices binned as
+// spins as hx_mixctx_apply_spin; out (nbins, l2max + 1) or (3, nbins, l2max + 1), host or device: the rows of the matrices binned as
 // heracles.result.binned does along axis -2 (weighted mean per bin; exactly 0 where the weighted sum is exactly 0).
-extern "C" int hx_mixctx_apply_binned(hx_mixctx *x, const double *cl, int ncl, int kind, double *out)
+extern "C" int hx_mixctx_apply_binned_spin(hx_mixctx *x, const double *cl, int ncl, int s1, int s2, double *out)
 {
     HX_TRY(ensure_ready());
-    if (!x || !cl || !out || ncl < 1 || (kind != 1 && kind != 2 && kind != 4)) return fail(HX_ERR_ARG, "hx_mixctx_apply_binned: bad argument");
+    if (!x || !cl || !out || ncl < 1) return fail(HX_ERR_ARG, "hx_mixctx_apply_binned_spin: bad argument");
+    bool eb = false;
+    HX_TRY(mix_ctx_spins("hx_mixctx_apply_binned_spin", s1, s2, eb));
     MixCtx &c = x->c;
-    if (c.nbins < 1) return fail(HX_ERR_ARG, "hx_mixctx_apply_binned: no bins set (hx_mixctx_set_bins)");
+    if (c.nbins < 1) return fail(HX_ERR_ARG, "hx_mixctx_apply_binned_spin: no bins set (hx_mixctx_set_bins)");
     const int n2 = c.l2max + 1;
     const size_t sz = (size_t)c.nbins * n2;
     DevBuf &d_cl = mix_cache().cl;
     HX_TRY(stage_cl(cl, ncl, c.l3max, d_cl));
     HX_TRY(mix_ctx_mask(c, d_cl.as<double>()));
-    const size_t bytes = sizeof(double) * sz * (kind == 4 ? 3 : 1);
+    const size_t bytes = sizeof(double) * sz * (eb ? 3 : 1);
     const bool to_host = !is_device_ptr(out);
     if (to_host) HX_TRY(c.b_out.alloc(bytes));
     double *d_out = to_host ? c.b_out.as<double>() : out;
     hipStream_t st = rt().stream;
     const dim3 grid((n2 + 255) / 256, c.nbins);
-    if (kind == 4) {
-        HX_TRY(mix_ctx_binned_product(c, 2, 0));
-        HX_TRY(mix_ctx_binned_product(c, 3, 1));
+    if (eb) {
+        HX_TRY(mix_ctx_binned_product(c, s1, s2, 0));
+        HX_TRY(mix_ctx_binned_product(c, s1, -s2, 1));
         hipLaunchKernelGGL(k_binned_finish<true>, grid, dim3(256), 0, st, c.nbins, n2, c.nbpad, c.l2pad, c.ksplit, c.part[0].as<double>(), c.part[1].as<double>(),
                            c.d_cs.as<double>(), c.b_norm.as<double>(), d_out);
     } else {
-        HX_TRY(mix_ctx_binned_product(c, kind == 1 ? 0 : 1, 0));
+        HX_TRY(mix_ctx_binned_product(c, std::max(s1, s2), 0, 0));
         hipLaunchKernelGGL(k_binned_finish<false>, grid, dim3(256), 0, st, c.nbins, n2, c.nbpad, c.l2pad, c.ksplit, c.part[0].as<double>(), (const double *)nullptr,
                            c.d_cs.as<double>(), c.b_norm.as<double>(), d_out);
     }
@@ -1335,6 +1486,14 @@ extern "C" int hx_mixctx_apply_binned(hx_mixctx *x, const double *cl, int ncl, i
     }
     HX_HIP(hipStreamSynchronize(rt().stream));
     return HX_OK;
+}
+
+// kind as hx_mixctx_apply
+extern "C" int hx_mixctx_apply_binned(hx_mixctx *x, const double *cl, int ncl, int kind, double *out)
+{
+    int s1, s2;
+    if (!mix_kind_spins(kind, s1, s2)) return fail(HX_ERR_ARG, "hx_mixctx_apply_binned: bad argument");
+    return hx_mixctx_apply_binned_spin(x, cl, ncl, s1, s2, out);
 }
 
 // hx_cl2corr / hx_corr2cl live in hx_transforms.hip

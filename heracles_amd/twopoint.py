@@ -278,7 +278,7 @@ def _mm_args(cl, l1max, l2max, l3max):
 
 
 def mixmat(cl, l1max=None, l2max=None, l3max=None, spin=(0, 0), out=None):
-    """Mixing matrix of a mask spectrum for spins (0,0), (0,2) or (2,0); replaces
+    """Mixing matrix of a mask spectrum for spins (0,0), (s,0) or (0,s) of any spin weight s; replaces
     ``convolvecl.mixmat`` as called at heracles/twopoint.py:382-388.  Shape (l1max+1, l2max+1),
     axis 0 is the output multipole.  ``out``: an array the caller owns and re-uses (float64, that shape, C-contiguous; numpy --
     pageable or ``heracles_amd.pinned_empty`` -- or a torch tensor, host or device), filled and returned instead of a fresh one."""
@@ -291,15 +291,18 @@ def mixmat(cl, l1max=None, l2max=None, l3max=None, spin=(0, 0), out=None):
 
 
 def mixmat_eb(cl, l1max=None, l2max=None, l3max=None, spin=(2, 2), out=None):
-    """E/B mixing matrices (EE->EE, EE->BB, EB->EB); replaces ``convolvecl.mixmat_eb``.  ``out`` as in ``mixmat``, shape
+    """E/B mixing matrices (EE->EE, EE->BB, EB->EB) of two fields of any non-zero spin weights (by magnitude); replaces
+    ``convolvecl.mixmat_eb``.  With G^(ab) the quadrature form of hx_mixmat.hip: [0] = (G^(s1,s2) + G^(s1,-s2)) / 2,
+    [1] = (G^(s1,s2) - G^(s1,-s2)) / 2, [2] = G^(s1,-s2); a full-sky mask gives the identity on l >= max(s1, s2).  ``out`` as in ``mixmat``, shape
     (3, l1max+1, l2max+1): a build into a fresh numpy array pays the first touch of its pages (0.9 GB at L = 6144: more than the GPU
     spends on the matrices); a loop that hands every result on passes the same ``out`` each time."""
     cl, l1max, l2max, l3max = _mm_args(cl, l1max, l2max, l3max)
-    if tuple(abs(s) for s in spin) != (2, 2):
-        raise NotImplementedError(f"mixmat_eb for spin {spin} not supported")
+    s1, s2 = (abs(int(s)) for s in spin)
+    if not (s1 and s2):
+        raise NotImplementedError(f"mixmat_eb for spin {tuple(spin)} not supported: it needs two non-zero spins (use mixmat)")
     out = _lib.result_array((3, l1max + 1, l2max + 1), out)
     _lib.ensure_init()
-    _lib.check(_lib.load().hx_mixmat_eb(_lib.ptr(cl), cl.shape[0], l1max, l2max, l3max, _lib.ptr(out)))
+    _lib.check(_lib.load().hx_mixmat_eb_spin(_lib.ptr(cl), cl.shape[0], l1max, l2max, l3max, s1, s2, _lib.ptr(out)))
     return out
 
 
@@ -358,9 +361,8 @@ class MixmatContext:
         """A page-locked host array of the shape ``self(cl, spin)`` returns, owned by this context (one per shape, freed with it):
         pass it as ``out=`` for every matrix of a loop that consumes each result before the next build -- the GPU writes it by DMA,
         no staging copy, no page faults.  The NEXT call with the same ``out`` overwrites it."""
-        s1, s2 = (abs(int(v)) for v in spin)
         shape = (self.l1max + 1, self.l2max + 1)
-        if (s1, s2) == (2, 2):
+        if self._three(spin):
             shape = (3,) + shape
         if not hasattr(self, "_buffers"):
             self._buffers = {}
@@ -369,22 +371,17 @@ class MixmatContext:
         return self._buffers[shape]
 
     @staticmethod
-    def _kind(spin):
-        s1, s2 = (abs(int(v)) for v in spin)
-        if (s1, s2) == (0, 0):
-            return 1
-        if sorted((s1, s2)) == [0, 2]:
-            return 2
-        if (s1, s2) == (2, 2):
-            return 4
-        raise NotImplementedError(f"mixing matrix for spin {tuple(spin)} not supported")
+    def _three(spin):
+        """Two fields of non-zero spin weight have three matrices (``mixmat_eb``), every other pair one (``mixmat``)."""
+        s1, s2 = spin
+        return bool(int(s1) and int(s2))
 
     def __call__(self, cl, spin, out=None):
-        kind = self._kind(spin)
+        s1, s2 = (abs(int(v)) for v in spin)
         cl = np.ascontiguousarray(np.asarray(cl, dtype=np.float64))
         shape = (self.l1max + 1, self.l2max + 1)
-        out = _lib.result_array((3,) + shape if kind == 4 else shape, out)
-        _lib.check(_lib.load().hx_mixctx_apply(self._h, _lib.ptr(cl), cl.shape[0], kind, _lib.ptr(out)))
+        out = _lib.result_array((3,) + shape if self._three(spin) else shape, out)
+        _lib.check(_lib.load().hx_mixctx_apply_spin(self._h, _lib.ptr(cl), cl.shape[0], s1, s2, _lib.ptr(out)))
         return out
 
     def set_bins(self, plan):
@@ -404,15 +401,15 @@ class MixmatContext:
 
     def binned(self, cl, spin, out=None):
         """The matrices of ``self(cl, spin)`` with their rows binned by the plan of ``set_bins``: (nbins, l2max + 1), or
-        (3, nbins, l2max + 1) for spin (2, 2) -- ``heracles.result.binned(Result(M, axis=-2), edges, weights).array`` without the
+        (3, nbins, l2max + 1) for two non-zero spins -- ``heracles.result.binned(Result(M, axis=-2), edges, weights).array`` without the
         full matrix ever being formed (hx_mixctx_apply_binned)."""
         if getattr(self, "plan", None) is None:
             raise ValueError("no bins set: call set_bins first")
-        kind = self._kind(spin)
+        s1, s2 = (abs(int(v)) for v in spin)
         cl = np.ascontiguousarray(np.asarray(cl, dtype=np.float64))
         shape = (self.plan.nbins, self.l2max + 1)
-        out = _lib.result_array((3,) + shape if kind == 4 else shape, out)
-        _lib.check(_lib.load().hx_mixctx_apply_binned(self._h, _lib.ptr(cl), cl.shape[0], kind, _lib.ptr(out)))
+        out = _lib.result_array((3,) + shape if self._three(spin) else shape, out)
+        _lib.check(_lib.load().hx_mixctx_apply_binned_spin(self._h, _lib.ptr(cl), cl.shape[0], s1, s2, _lib.ptr(out)))
         return out
 
     def close(self):
@@ -514,7 +511,7 @@ def mixing_matrices(fields, cls, *, l1max=None, l2max=None, l3max=None, bins=Non
             return ctx(cl, spin), None
         if plan_for(a + 1).nbins == 0:  # (a single edge: no bin at all -- empty rows, as the reference returns them)
             plan = plan_for(a + 1)
-            shape = (3, 0, b + 1) if MixmatContext._kind(spin) == 4 else (0, b + 1)
+            shape = (3, 0, b + 1) if MixmatContext._three(spin) else (0, b + 1)
             return np.zeros(shape), plan
         return ctx.binned(cl, spin), ctx.plan
 

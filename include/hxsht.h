@@ -182,8 +182,15 @@ int hx_gauss_legendre(int n, double *x, double *w);
  * (tests/test_gpu_mixmat.py::test_mixmat_blocks_at_high_l_vs_3j). */
 int hx_gauss_legendre_dd(int n, double *x, double *w, double *xlo);
 
-/* D[k][l] = d^l_{ab}(x_k), l = 0..lmax, (a,b) in {(0,0),(2,0),(2,2),(2,-2),(1,1),(-1,1)} (zero below max(|a|,|b|));
- * out is [n][lmax+1] row-major.  (Functions of heracles/transforms.py:46-112: P_l, d20, d22, d2m2, d11, dm11.)       */
+/* Largest spin weight the Wigner-d tables and the mixing matrices serve.  The recursion in l starts from
+ * d^a_{ab}(x) ~ ((1 -+ x)/2)^{(a -+ b)/2}: about (1.7e-8)^{s/2} at the polar node of an L = 6144 build, which leaves the double range
+ * near s = 80; up to 32 the seed stays above 1e-125 and every error-free product of the double-double arithmetic far from the
+ * denormals.  Beyond it: HX_ERR_UNSUPPORTED (not tables of zeros). */
+#define HX_MAX_MIX_SPIN 32
+/* D[k][l] = d^l_{ab}(x_k), l = 0..lmax, any (a,b) with max(|a|,|b|) <= HX_MAX_MIX_SPIN (zero below max(|a|,|b|), also when that
+ * lies beyond lmax); out is [n][lmax+1] row-major.  (Functions of heracles/transforms.py:46-112: P_l, d20, d22, d2m2, d11, dm11, and
+ * the same for every other pair.)  Test hook: env HX_WIGNER_SEED=general starts the recursion of the pairs named above from the
+ * general seed as well (the results must not differ in a bit). */
 int hx_wigner_d_table(int lmax, int a, int b, int n, const double *x, double *out);
 
 /* Replaces convolvecl.mixmat / mixmat_eb as called at heracles/twopoint.py:378-388.
@@ -192,6 +199,14 @@ int hx_wigner_d_table(int lmax, int a, int b, int n, const double *x, double *ou
 int hx_mixmat(const double *cl, int ncl, int l1max, int l2max, int l3max, int s1, int s2,
               double *out);
 int hx_mixmat_eb(const double *cl, int ncl, int l1max, int l2max, int l3max, double *out);
+/* Fields of any spin weights (what heracles.twopoint.mixing_matrices hands to convolvecl for any two fields, heracles/twopoint.py:375-388),
+ * spins by magnitude, up to HX_MAX_MIX_SPIN.  The matrices are DEFINED by the quadrature form
+ *   G^{(ab)} = D^{(ab)T} diag(w xi) D^{(ab)} diag((2 l2 + 1)/2),  D^{(ab)}[k][l] = d^l_{ab}(x_k),
+ * i.e. (-1)^{s1+s2} times the bare product of 3j symbols: a full-sky mask gives the identity for every pair of spins.
+ *   hx_mixmat: (s, 0) and (0, s) for any s: G^{(s,0)}; two non-zero spins: HX_ERR_UNSUPPORTED.
+ *   hx_mixmat_eb_spin: two non-zero spins, out [3][l1max+1][l2max+1] = (G^{(s1,s2)} + G^{(s1,-s2)}) / 2, (G^{(s1,s2)} - G^{(s1,-s2)}) / 2,
+ *     G^{(s1,-s2)} (the roles of heracles/twopoint.py:445-458, 505-508); hx_mixmat_eb is hx_mixmat_eb_spin(2, 2). */
+int hx_mixmat_eb_spin(const double *cl, int ncl, int l1max, int l2max, int l3max, int s1, int s2, double *out);
 /* hx_mixmat / hx_mixmat_eb / hx_mixmat_batch keep the mask-independent part of their last build (nodes and Wigner-d tables of one
  * (l1max, l2max, l3max)) and the staging buffer of a host destination in HBM between calls (~3 GB at L = 6144), so that the next
  * build of that size allocates nothing; this frees them.  (The reference rebuilds everything per convolvecl call,
@@ -259,6 +274,13 @@ int hx_pinv(int n, int m, const double *M, double rcond, double *out, double *in
 typedef struct hx_mixctx hx_mixctx;
 hx_mixctx *hx_mixctx_create(int l1max, int l2max, int l3max);
 int hx_mixctx_apply(hx_mixctx *ctx, const double *cl, int ncl, int kind, double *out);
+/* The same for any two spins (by magnitude, <= HX_MAX_MIX_SPIN): one of them zero -> one matrix (hx_mixmat), both non-zero -> three
+ * (hx_mixmat_eb_spin).  kind 1 / 2 / 4 of hx_mixctx_apply are (0,0) / (2,0) / (2,2) here, bit for bit.
+ * A context keeps one Wigner-d table per normalised pair (a >= |b|: (s1, s2) and (s2, s1) share theirs), built on first use:
+ * (l + 1 padded to 128) x (nodes padded to 32) doubles each, 0.46 GB at L = 6144.  The (0,0) table always stays (the node weights of
+ * every mask read it); of the others at most 16 (env HX_MIX_TABLES=n at hx_mixctx_create, n >= 1) are kept, enough for every pair of a
+ * job with spins {0, 1, 2, 3}, and the one used longest ago is dropped for a new one. */
+int hx_mixctx_apply_spin(hx_mixctx *ctx, const double *cl, int ncl, int s1, int s2, double *out);
 void hx_mixctx_destroy(hx_mixctx *ctx);
 /* The rows of those matrices BINNED, as heracles.twopoint.mixing_matrices(..., bins, weights) returns them (heracles/twopoint.py:391-397:
  * heracles.result.binned along axis -2, heracles/result.py:124-248 -- what heracles/cli.py:696-716 asks for whenever the configuration
@@ -271,6 +293,7 @@ void hx_mixctx_destroy(hx_mixctx *ctx);
  *     out[b][l2] = sum_{l in b} w_l M[l][l2] / norm[b], exactly 0 where the sum is exactly 0 (heracles/result.py:132-135). */
 int hx_mixctx_set_bins(hx_mixctx *ctx, int nbins, const int *which, const double *w, const double *norm);
 int hx_mixctx_apply_binned(hx_mixctx *ctx, const double *cl, int ncl, int kind, double *out);
+int hx_mixctx_apply_binned_spin(hx_mixctx *ctx, const double *cl, int ncl, int s1, int s2, double *out); /* spins as hx_mixctx_apply_spin */
 /* The same loop as ONE call over a list of masks:
  *   cls   [nmask][ncl] mask spectra; kinds [nmask] bit mask: 1 -> spin (0,0) into out00[k]; 2 -> spin (0,2)/(2,0) into
  *   out02[k]; 4 -> spin (2,2) into outeb[k] (3 matrices as hx_mixmat_eb).  Output pointers host or device. */
