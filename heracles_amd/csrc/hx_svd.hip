@@ -106,8 +106,10 @@ __global__ __launch_bounds__(256) void k_svd_eig(const double *__restrict__ G, d
         for (int e = t; e < SP * SP; e += 256) {
             const int i = e >> 6, j = e & 63;
             if (i < j) {
-                const double d = A[i][i] * A[j][j];
-                if (d > 0.0 && A[i][i] > null2 && A[j][j] > null2) mx = fmax(mx, fabs(A[i][j]) / sqrt(d));
+                // sqrt(G_ii) sqrt(G_jj), not sqrt(G_ii G_jj): the product of two squared norms leaves the double range (and the pair the
+                // measure) for |M| beyond 1e+-77, long before a squared norm does
+                const double d = sqrt(A[i][i]) * sqrt(A[j][j]);
+                if (d > 0.0 && A[i][i] > null2 && A[j][j] > null2) mx = fmax(mx, fabs(A[i][j]) / d);
             }
         }
         atomicMax(&lmax_bits, (unsigned long long)__double_as_longlong(mx));
@@ -130,8 +132,8 @@ __global__ __launch_bounds__(256) void k_svd_eig(const double *__restrict__ G, d
                     if (p > q) { const int z = p; p = q; q = z; }
                     const double app = A[p][p], aqq = A[q][q], apq = A[p][q];
                     double c = 1.0, s = 0.0;
-                    const double dd = app * aqq;
-                    const double rel = dd > 0.0 ? fabs(apq) / sqrt(dd) : (apq != 0.0 ? 1.0 : 0.0);
+                    const double dd = sqrt(app) * sqrt(aqq);   // (the two roots are independent: the latency of one, as before)
+                    const double rel = dd > 0.0 ? fabs(apq) / dd : (apq != 0.0 ? 1.0 : 0.0);
                     if (rel > 1e-17 && apq != 0.0) {
                         const double tau = (aqq - app) / (2.0 * apq);
                         const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
@@ -354,6 +356,10 @@ extern "C" int hx_pinv(int n, int m, const double *M, double rcond, double *out,
         HX_HIP(hipStreamSynchronize(st));
         for (double v : c2) fro2 += v;
     }
+    // a NaN or an infinity in M (or squared norms that overflow) makes fro2, and with it null2, non-finite: every comparison with null2 in
+    // k_svd_eig is then false, the measure is 0 and the first sweep would "converge" on garbage.  numpy.linalg.pinv raises here too
+    if (!std::isfinite(fro2))
+        return fail(HX_ERR_ARG, "hx_pinv: the matrix holds a NaN or an infinity, or its squared Frobenius norm overflows (sum of squares = %g)", fro2);
     const double null2 = 1e-30 * fro2;
     int sweeps = 0;
     bool converged = false;
@@ -384,17 +390,26 @@ extern "C" int hx_pinv(int n, int m, const double *M, double rcond, double *out,
         return fail(HX_ERR_UNSUPPORTED, "hx_pinv: the Jacobi sweeps did not converge (%d sweeps, largest |G_ij| / sqrt(G_ii G_jj) = %.3e, tolerance %.3e)", sweeps, last_off, tol);
     // singular values, cut-off, pinv = V diag(mask / sigma^2) W^T
     hipLaunchKernelGGL(k_svd_colnorm2, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, W.as<double>(), ld, nw, (int)ld, d_s.as<double>());
-    std::vector<double> s2(ld);
+    std::vector<double> s2(ld), v2(ld);
     HX_HIP(hipMemcpyAsync(s2.data(), d_s.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
+    // W = M V holds to rounding whatever the rotations were, so sigma_j = |w_j| / |v_j|.  |v_j| is 1 only as far as the thousands of 64 x 64
+    // rotations a column went through were orthogonal: their common rounding drift is in |w_j| and |v_j| alike (at 2240 x 2079, 31 sweeps,
+    // |w_j| alone gave the largest and the smallest kept singular value 9e-13 and 8e-13 too large).  The product below needs no such care: v_j w_j^T / |w_j|^2 = v^_j u_j^T / sigma_j exactly
     HX_HIP(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_svd_colnorm2, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, st, V.as<double>(), ld, (int)ld, (int)ld, d_s.as<double>());
+    HX_HIP(hipMemcpyAsync(v2.data(), d_s.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    std::vector<double> sg(ld);
     double smax = 0.0;
-    for (double v : s2) smax = std::max(smax, std::sqrt(v));
+    for (long long j = 0; j < ld; ++j) {
+        sg[j] = v2[j] > 0.0 ? std::sqrt(s2[j] / v2[j]) : 0.0;
+        smax = std::max(smax, sg[j]);
+    }
     int kept = 0;
     double smin = smax;
-    for (double &v : s2) {
-        const double sg = std::sqrt(v);
-        if (sg > rcond * smax && sg > 0.0) { ++kept; smin = std::min(smin, sg); v = 1.0 / v; }
-        else v = 0.0;
+    for (long long j = 0; j < ld; ++j) {
+        if (sg[j] > rcond * smax && sg[j] > 0.0) { ++kept; smin = std::min(smin, sg[j]); s2[j] = 1.0 / s2[j]; }
+        else s2[j] = 0.0;
     }
     HX_HIP(hipMemcpyAsync(d_s.p, s2.data(), sizeof(double) * ld, hipMemcpyHostToDevice, st));
     // pinv(Wm) (mw x nw) = V S W^T; the caller's pinv(M) is that (M tall) or its transpose (M wide: pinv(M) = pinv(M^T)^T)

@@ -599,12 +599,29 @@ def apply_mixing_matrix(d, M):
 # ---- heracles.twopoint.invert_mixing_matrix (heracles/twopoint.py:404-494) ---------------------------------------------
 def pinv(M, rcond=1e-5, *, device=None, info=False):
     """``np.linalg.pinv(M, rcond=rcond)`` on the GPU (``hx_pinv``: blocked one-sided Jacobi SVD, singular values <= rcond * the largest
-    dropped).  ``M``: numpy array or device tensor (n, m); returns a numpy array (m, n), or a device tensor with ``device=``."""
+    dropped).  ``M``: numpy array or torch tensor (host or device), exactly two-dimensional (n, m); anything else is a ``ValueError``.
+    Either kind is converted to contiguous float64 first (a float32 or integer input gives the result of its float64 copy, a transposed
+    view that of its contiguous copy).  Returns a numpy array (m, n), or a device tensor with ``device=``.  ``info=True`` adds a dict:
+    ``sweeps`` of the one-sided iteration, singular values ``kept``, the ``largest`` and the ``smallest_kept`` singular value.
+
+    A NaN or an infinity in ``M`` raises ``HxError`` (``np.linalg.pinv`` raises ``LinAlgError``), as does a matrix whose sweeps do not
+    converge; nothing is written then.  Every measure inside is relative, so ``pinv(c M) = pinv(M) / c`` to rounding, as long as the
+    squared norms stay inside the double range: the sum of all squared entries must stay finite, and 1e-30 of it, the level below which
+    a column counts as null, a normal number -- about 1e-139 < |M|_F < 1e154 (pinned at 2^+-300 = 2e+-90)."""
     import ctypes as C_
 
     M = getattr(M, "tensor", M)
+    if hasattr(M, "data_ptr"):
+        import torch
+
+        if M.dim() != 2:
+            raise ValueError(f"pinv wants a two-dimensional matrix, got shape {tuple(M.shape)}")
+        M = M.to(torch.float64).contiguous()
+    else:
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.ndim != 2:
+            raise ValueError(f"pinv wants a two-dimensional matrix, got shape {M.shape}")
     n, m = M.shape
-    M = M.contiguous() if hasattr(M, "data_ptr") else np.ascontiguousarray(M, dtype=np.float64)
     if device is None:
         out = np.empty((m, n))
     else:
