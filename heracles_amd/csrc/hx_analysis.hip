@@ -746,40 +746,23 @@ __global__ __launch_bounds__(256) void k_alm_reduce_spin(int lmax, int s, const 
 // =====================================================================================
 // host side: task list, m-chunking, launch sequence
 // =====================================================================================
-// libsharp's published heuristic for the largest m that contributes on a ring
-// (sharp_get_mlim): rings with m > mlim are skipped.
-static int ring_mlim(int lmax, int spin, double sth, double cth)
-{
-    double ofs = lmax * 0.01;
-    if (ofs < 100.) ofs = 100.;
-    double b = -2 * spin * fabs(cth);
-    double t1 = lmax * sth + ofs;
-    double c = (double)spin * spin - t1 * t1;
-    double discr = b * b - 4 * c;
-    if (discr <= 0) return lmax;
-    double res = (-b + sqrt(discr)) / 2.;
-    if (res > lmax) res = lmax;
-    return (int)(res + 0.5);
-}
-
 // Column layout of one sweep over nb components (2 real columns per spin-0 map, 4 per spin-2 field):
 //   cols <= 8 : no matrix instruction at all -- one sweep per map / field of the vector-unit kernel (valu);
 //   else      : ng full 16-column groups + nbx extra 4-column blocks on the pipelined kernel.
 // The pipelined kernel is matrix-bound, so a sweep costs what its (4-column padded) columns cost whatever the
 // split; 32 columns is what the B operands of two ring sets leave of the register file.
 struct SweepShape {
-    int ng, nbx, valu, ncol, oneset, duo;
+    int ng, nbx, valu, ncol, duo;
 };
 static SweepShape sweep_shape(int spin, int nb)
 {
     const int cols = 2 * nb;
-    SweepShape sh = {0, 0, 0, 0, 0, 0};
+    SweepShape sh = {0, 0, 0, 0, 0};
     // <= 4 spin-0 maps / <= 2 spin-2 fields: one sweep per map / field on the vector unit (hx_legendre_valu.hip)
     if (cols <= 8) { sh.valu = 1; return sh; }
     // k_legendre_duo: one ring set per wave; spin 2 keeps one operand of the two positions in registers (HALFB): up to two 16-column
     // groups + two 4-column blocks (ten fields); spin 0 one group + one block (ten maps) or two groups (sixteen)
     sh.duo = 1;
-    sh.oneset = spin == 2;  // (task set of 4 ring blocks)
     sh.ng = std::max(cols / NCOL, 1);
     const int rem = cols > NCOL ? cols % NCOL : 0;
     const int maxbx = spin == 2 ? 2 : (sh.ng == 1 ? 1 : 0);
@@ -836,51 +819,10 @@ int analysis_max_batch(int spin, int ncomp)
     return mx;
 }
 
-// ts[0], ts[1]: spin 0 / spin 2 tasks of NW ring blocks (ts[3]: one ring set per wave; ts[4], ts[5]: the vector-unit kernel)
-static int build_task_set(hx_plan *pl, int spin, int nw, hx_plan::TaskSet &ts);
-int build_tasks(hx_plan *pl, int spin)
-{
-    return build_task_set(pl, spin, spin == 0 ? LegCfg<0>::NW : LegCfg<2>::NW, pl->ts[spin ? 1 : 0]);
-}
-static int build_task_set(hx_plan *pl, int spin, int nw, hx_plan::TaskSet &ts)
-{
-    if (ts.built) return HX_OK;
-    const int lmax = pl->lmax;
-    const int nrb = (pl->nrp + RBLK - 1) / RBLK;
-    ts.tasks.clear();
-    ts.of_m.assign(lmax + 1, MTasks{0, 0});
-    ts.rows_before_m.assign(lmax + 2, 0);
-    ts.arow.assign(lmax + 2, 0);
-    long long rows = 0, arows = 0;
-    // mlim is monotone in the ring index (pole -> equator): first active ring by bisection
-    std::vector<int> mlim(pl->nrp);
-    for (int rp = 0; rp < pl->nrp; ++rp) mlim[rp] = ring_mlim(lmax, spin, pl->h_sth[rp], pl->h_z[rp]);
-    for (int m = 0; m <= lmax; ++m) {
-        ts.rows_before_m[m] = rows;
-        ts.arow[m] = arows;
-        const int l0 = std::max(m, spin);
-        if (l0 <= lmax) arows += (long long)LBLK * ((lmax - l0) / LBLK + 1);
-        ts.of_m[m].first = (int)ts.tasks.size();
-        if (l0 <= lmax) {
-            int first = (int)(std::lower_bound(mlim.begin(), mlim.end(), m) - mlim.begin());
-            if (first >= pl->nrp) first = pl->nrp - 1;
-            for (int rb = first / RBLK; rb < nrb; rb += nw) {
-                LegTask t;
-                t.m = m; t.rb0 = rb; t.nrb = std::min(nw, nrb - rb); t.pad = 0; t.pout = rows;
-                rows += (long long)LBLK * ((lmax - l0) / LBLK + 1);  // padded to whole 32-l blocks (the pipelined kernel stores unconditionally)
-                ts.tasks.push_back(t);
-            }
-        }
-        ts.of_m[m].count = (int)ts.tasks.size() - ts.of_m[m].first;
-    }
-    ts.rows_before_m[lmax + 1] = rows;
-    ts.arow[lmax + 1] = arows;
-    HX_TRY(upload(ts.d_tasks, ts.tasks));
-    HX_TRY(upload(ts.d_of_m, ts.of_m));
-    HX_TRY(upload(ts.d_arow, ts.arow));
-    ts.built = true;
-    return HX_OK;
-}
+// Ring blocks per task (the key of task_set, hx_plan.hip).  k_legendre_duo and k_synth_duo: one ring set per wave, 8 (spin 0) / 4 (spin 2);
+// the flop accounting and the pruning of hx_ring_modes: the 16 / 8 of the first matrix kernel, which the quoted figures were counted with
+int one_set_task_blocks(int spin) { return PipeCfg<2>::NW * (spin ? PipeCfg<2>::RBS : PipeCfg<0>::RBS); }
+int flop_task_blocks(int spin) { return spin == 0 ? LegCfg<0>::NW : LegCfg<2>::NW; }
 
 static bool duo_shape(const SweepShape &sh) { return sh.duo != 0; }
 // doubles per accumulation row of a sweep: the rows of the 36- and 40-column shapes start on 128-byte lines (the atomics of a flush -- 16
@@ -907,8 +849,23 @@ static int launch_duo(const SweepShape &sh, dim3 pgrid, hipStream_t st, const Le
     return HX_OK;
 }
 
+// rows of the partial buffer -> alms (x fl) for the orders m0 + k ms, k < nm, of a sweep of the specialised kernels; al: the scalings of a
+// sweep of k_legendre_duo (one span of rows per m), null for the vector-unit kernels (one span per ring group, summed here)
+static void launch_alm_reduce(hx_plan *pl, int spin, hx_plan::TaskSet &ts, long long row0, int m0, int ms, int nm, int nb, int ng, int pcol,
+                              const double *d_fl, int add, double2 *d_alms, const double *al)
+{
+    const PlanDev P = pl->dev();
+    const long long *arow = al ? ts.d_arow.as<long long>() : nullptr;
+    if (spin == 0)
+        hipLaunchKernelGGL(k_alm_reduce<0>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->partial.as<double>(),
+                           row0, m0, ms, nb, ng, pcol, d_fl, add, d_alms, pl->nlm, arow, al);
+    else
+        hipLaunchKernelGGL(k_alm_reduce<2>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->partial.as<double>(),
+                           row0, m0, ms, nb, ng, pcol, d_fl, add, d_alms, pl->nlm, arow, al);
+}
+
 template <int SPIN>
-static int launch_chunk(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int nb, const SweepShape &sh, const double *d_rw,
+static int launch_chunk(hx_plan *pl, hx_plan::SpinData &sd, hx_plan::TaskSet &ts, int m0, int m1, int nb, const SweepShape &sh, const double *d_rw,
                         const double *d_fl, int add, double2 *d_alms)
 {
     // column groups of the F / partial rows: full groups (+ 1 holding the extra blocks)
@@ -934,14 +891,11 @@ static int launch_chunk(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int n
         A.of_m = ts.d_of_m.as<MTasks>(); A.arow = ts.d_arow.as<long long>(); A.arow0 = ts.arow[m0]; A.add_all = 0;
         A.tasks = ts.d_tasks.as<LegTask>();  // (the kernel indexes the whole list through of_m)
         // (no memset of the rows: the first ring group of an m stores them)
-        const double2 *cn = SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
-        HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, cn));
+        HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, sd.cn.as<double2>()));
     }
     {
         ProfScope ps("alm_reduce");
-        hipLaunchKernelGGL(k_alm_reduce<SPIN>, dim3(nm), dim3(256), 0, st, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
-                           pl->partial.as<double>(), ts.arow[m0], m0, ms, nb, ng, pcol, d_fl, add, d_alms, pl->nlm, ts.d_arow.as<long long>(),
-                           SPIN == 0 ? pl->al0.as<double>() : pl->al2.as<double>());
+        launch_alm_reduce(pl, SPIN, ts, ts.arow[m0], m0, ms, nm, nb, ng, pcol, d_fl, add, d_alms, sd.al.as<double>());
     }
     HX_HIP(hipGetLastError());
     return HX_OK;
@@ -951,100 +905,69 @@ static int launch_chunk(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int n
 // The ring Fourier stage runs once for the whole batch.
 static bool valu_batch(int spin, int nb) { return sweep_shape(spin, nb).valu != 0; }
 
-int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **out, int blocks, bool generic)
+// Scratch budget of the m-chunks of an analysis on this plan: hx_set_scratch_budget() / HX_SCRATCH_GB, else 80 GB but never more than
+// half of what is free on the device (what this plan already holds for F / partial counts as free), and at least 2 GB
+static double analysis_budget(const hx_plan *pl)
 {
-    if (generic) {  // tables and tasks of this spin weight: never those of spin 2
-        hx_plan::SpinSet *set = nullptr;
-        HX_TRY(ensure_rec_s(pl, spin, &set));
-        HX_TRY(build_task_set(pl, spin, valu_task_blocks(spin), set->ts));
-        *out = &set->ts;
-        return HX_OK;
-    }
-    if (spin) HX_TRY(ensure_rec2(pl));
-    if (blocks <= 0) blocks = valu_task_blocks(spin);
-    if (blocks != valu_task_blocks(spin) && blocks != 8) return fail(HX_ERR_ARG, "valu_tasks: %d ring blocks per task", blocks);
-    hx_plan::TaskSet &ts = blocks == 8 && blocks != valu_task_blocks(spin) ? (spin ? pl->ts[6] : pl->ts[7]) : (spin ? pl->ts[4] : pl->ts[5]);
-    HX_TRY(build_task_set(pl, spin, blocks, ts));
-    *out = &ts;
-    return HX_OK;
-}
-
-int synth_duo_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **out)
-{
-    if (spin) HX_TRY(ensure_rec2(pl));
-    hx_plan::TaskSet &ts = spin ? pl->ts[3] : pl->ts[2];
-    HX_TRY(build_task_set(pl, spin, PipeCfg<2>::NW * (spin ? PipeCfg<2>::RBS : PipeCfg<0>::RBS), ts));
-    // the highest order every ring pair is synthesised for: the tasks of an order m start at the 32-ring-pair block that holds the first
-    // ring with mlim >= m (build_task_set), so ring pair rp is covered for m <= the largest mlim of its block; the rows beyond are never
-    // written and the spectrum pass does not read them (no 32 GB memset per sweep of ten fields)
-    DevBuf &lim = spin ? pl->syn_mlim2 : pl->syn_mlim0;
-    if (!lim.p) {
-        std::vector<int> h(pl->nrp_pad, -1);
-        for (int rp = 0; rp < pl->nrp; ++rp) {
-            const int last = std::min(rp / RBLK * RBLK + RBLK - 1, pl->nrp - 1);
-            h[rp] = std::min(pl->lmax, ring_mlim(pl->lmax, spin, pl->h_sth[last], pl->h_z[last]));
-        }
-        HX_TRY(upload(lim, h));
-    }
-    *out = &ts;
-    return HX_OK;
-}
-
-static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
-                               const double *d_pw, const double *d_fl, int add, bool generic = false)
-{
-    hx_plan::TaskSet *tsp = nullptr;
-    HX_TRY(valu_tasks(pl, spin, &tsp, 0, generic));
-    hx_plan::TaskSet &ts = *tsp;
-    if (pl->hsrc == nullptr && pl->nssrc == nullptr) {
-        HX_TRY(pl->Y.alloc(sizeof(double2) * (size_t)pl->ny * nb));
-        HX_TRY(launch_ring_subdft_maps(pl, nb, d_maps, d_pw, pl->Y.as<double2>()));
-    }
+    if (scratch_budget_bytes() > 0.0) return scratch_budget_bytes();
     double budget = 80e9;
-    if (scratch_budget_bytes() > 0.0) budget = scratch_budget_bytes();
-    else {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::min(budget, 0.5 * (double)(fr + pl->F.bytes + pl->partial.bytes));
-        budget = std::max(budget, 2e9);
-    }
-    const int lmax = pl->lmax, pcol = valu_partial_cols(spin), unit = spin ? 2 : 1;
-    const double f_per_m = (double)pl->nrp_pad * valu_operand_doubles(spin) * sizeof(double);
-    const std::vector<long long> &prow = ts.rows_before_m;
-    std::vector<std::pair<int, int>> chunks;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::min(budget, 0.5 * (double)(fr + pl->F.bytes + pl->partial.bytes));
+    return std::max(budget, 2e9);
+}
+
+// The m-chunks of a sweep whose operands take f_per_m bytes per order and whose partial sums take row_bytes per row of the prefix table
+// prow (rows before every m), within the budget; sizes F and partial for the largest chunk and notes the count for hx_plan_last_chunks.
+// A chunk [m0, m1) holds the orders m0, m0 + ms, ... < m1 (ms = 1 but on the m-sharded route); m1 - 1 is its last order
+static int plan_m_chunks(hx_plan *pl, double f_per_m, const std::vector<long long> &prow, size_t row_bytes, std::vector<std::pair<int, int>> &chunks)
+{
+    const double budget = analysis_budget(pl);
     size_t maxF = 16, maxP = 16;
-    // a chunk [m0, m1) holds the orders m0, m0 + ms, ... < m1 (ms = 1 but on the m-sharded route); m1 - 1 is its last order
-    const int m_end = pl->m_hi < 0 ? lmax + 1 : std::min(pl->m_hi, lmax + 1), ms = std::max(pl->m_step, 1);
+    const int m_end = pl->m_hi < 0 ? pl->lmax + 1 : std::min(pl->m_hi, pl->lmax + 1), ms = std::max(pl->m_step, 1);
     for (int m0 = std::max(pl->m_lo, 0); m0 < m_end;) {
         int last = m0;  // a chunk holds at least one m, whatever the budget
         while (last + ms < m_end) {
-            const double bytes = f_per_m * ((last + ms - m0) / ms + 1) + (double)(prow[last + ms + 1] - prow[m0]) * pcol * sizeof(double);
+            const double bytes = f_per_m * ((last + ms - m0) / ms + 1) + (double)(prow[last + ms + 1] - prow[m0]) * row_bytes;
             if (bytes > budget) break;
             last += ms;
         }
         const int m1 = last + 1;
         chunks.emplace_back(m0, m1);
         maxF = std::max(maxF, (size_t)(f_per_m * ((m1 - m0 + ms - 1) / ms)));
-        maxP = std::max(maxP, (size_t)(prow[m1] - prow[m0]) * pcol * sizeof(double));
+        maxP = std::max(maxP, (size_t)(prow[m1] - prow[m0]) * row_bytes);
         m0 = last + ms;
     }
     HX_TRY(pl->F.alloc(maxF));
     HX_TRY(pl->partial.alloc(maxP));
     pl->last_chunks = (int)chunks.size();
-    PlanDev P = pl->dev();
+    return HX_OK;
+}
+
+static int analysis_batch_valu(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
+                               const double *d_pw, const double *d_fl, int add, bool generic = false)
+{
+    hx_plan::SpinData *sd = nullptr;  // (generic: tables and tasks of this weight's own family, never those of spin 2)
+    hx_plan::TaskSet *tsp = nullptr;
+    HX_TRY(spin_data(pl, spin, generic, &sd));
+    HX_TRY(task_set(pl, spin, generic, valu_task_blocks(spin), &tsp));
+    hx_plan::TaskSet &ts = *tsp;
+    if (pl->hsrc == nullptr && pl->nssrc == nullptr) {
+        HX_TRY(pl->Y.alloc(sizeof(double2) * (size_t)pl->ny * nb));
+        HX_TRY(launch_ring_subdft_maps(pl, nb, d_maps, d_pw, pl->Y.as<double2>()));
+    }
+    const int lmax = pl->lmax, pcol = valu_partial_cols(spin), unit = spin ? 2 : 1, ms = std::max(pl->m_step, 1);
+    std::vector<std::pair<int, int>> chunks;
+    HX_TRY(plan_m_chunks(pl, (double)pl->nrp_pad * valu_operand_doubles(spin) * sizeof(double), ts.rows_before_m, pcol * sizeof(double), chunks));
     for (int c0 = 0; c0 < nb; c0 += unit)
         for (auto &ch : chunks) {
             const int m0 = ch.first, m1 = ch.second, nm = (m1 - m0 + ms - 1) / ms;
-            HX_TRY(launch_valu_chunk(pl, spin, ts, m0, m1, c0, d_rw, generic));
+            HX_TRY(launch_valu_chunk(pl, spin, *sd, ts, m0, m1, c0, d_rw, generic));
             ProfScope ps("alm_reduce");
             if (generic)
                 hipLaunchKernelGGL(k_alm_reduce_spin, dim3(nm), dim3(256), 0, rt().stream, lmax, spin, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
                                    pl->partial.as<double>(), ts.rows_before_m[m0], m0, ms, d_fl, add, d_alms + (size_t)c0 * pl->nlm, pl->nlm);
-            else if (spin == 0)
-                hipLaunchKernelGGL(k_alm_reduce<0>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
-                                   pl->partial.as<double>(), ts.rows_before_m[m0], m0, ms, 1, 1, pcol, d_fl, add, d_alms + (size_t)c0 * pl->nlm, pl->nlm, nullptr, nullptr);
             else
-                hipLaunchKernelGGL(k_alm_reduce<2>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
-                                   pl->partial.as<double>(), ts.rows_before_m[m0], m0, ms, 2, 1, pcol, d_fl, add, d_alms + (size_t)c0 * pl->nlm, pl->nlm, nullptr, nullptr);
+                launch_alm_reduce(pl, spin, ts, ts.rows_before_m[m0], m0, ms, nm, unit, 1, pcol, d_fl, add, d_alms + (size_t)c0 * pl->nlm, nullptr);
             HX_HIP(hipGetLastError());
         }
     return HX_OK;
@@ -1069,62 +992,24 @@ int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 
         return analysis_batch_valu(pl, spin, nb, d_maps, d_alms, d_rw, d_pw, d_fl, add, true);
     }
     if (valu_batch(spin, nb)) return analysis_batch_valu(pl, spin, nb, d_maps, d_alms, d_rw, d_pw, d_fl, add);
-    const int sidx = spin ? 1 : 0;
-    HX_TRY(build_tasks(pl, spin));
-    if (spin) HX_TRY(ensure_rec2(pl));
-    // doubles per F / partial row: only the columns in use are stored -- 4-column granularity on the
-    // 4x4x4 path (<= 8 columns), 16 per full group + 4 per extra block on the pipelined kernel
+    // k_legendre_duo: one ring set per wave; only the columns in use are stored (16 per full group + 4 per extra block)
     const SweepShape sh = sweep_shape(spin, nb);
-    // one ring set per wave: 4 (spin 2) / 8 (spin 0) ring blocks per task
-    const bool one_set = sh.oneset || duo_shape(sh);  // (spin 0: 8 ring blocks per task in ts[2])
-    if (one_set) HX_TRY(build_task_set(pl, spin, PipeCfg<2>::NW * (spin ? PipeCfg<2>::RBS : PipeCfg<0>::RBS), spin ? pl->ts[3] : pl->ts[2]));
-    hx_plan::TaskSet &ts = one_set ? (spin ? pl->ts[3] : pl->ts[2]) : pl->ts[sidx];
-    const int ncol = sh.ncol;
+    hx_plan::TaskSet *ts = nullptr;
+    hx_plan::SpinData *sd = nullptr;
+    HX_TRY(spin_data(pl, spin, false, &sd));
+    HX_TRY(task_set(pl, spin, false, one_set_task_blocks(spin), &ts));
     if (pl->hsrc == nullptr && pl->nssrc == nullptr) {
         HX_TRY(pl->Y.alloc(sizeof(double2) * (size_t)pl->ny * nb));
         HX_TRY(launch_ring_subdft_maps(pl, nb, d_maps, d_pw, pl->Y.as<double2>()));
     }
-
-    // budget: hx_set_scratch_budget() / HX_SCRATCH_GB, else 80 GB but never more than half of what is free on
-    // the device (what this plan already holds for F / partial counts as free)
-    double budget = 80e9;
-    if (scratch_budget_bytes() > 0.0) budget = scratch_budget_bytes();
-    else {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-            budget = std::min(budget, 0.5 * (double)(fr + pl->F.bytes + pl->partial.bytes));
-        budget = std::max(budget, 2e9);
-    }
-    const double f_per_m = (double)pl->nrp_pad * analysis_f_rows(spin) * ncol * sizeof(double);
-    const int lmax = pl->lmax;
-    // rows of the partial buffer: one span per m (the pipelined kernel adds its ring groups in place)
-    const std::vector<long long> &prow = ts.arow;
-    const int pcol = sweep_pcol(sh);  // doubles per row of the partial buffer (launch_chunk)
+    // rows of the partial buffer: one span per m (the pipelined kernel adds its ring groups in place), sweep_pcol doubles each
     std::vector<std::pair<int, int>> chunks;
-    size_t maxF = 16, maxP = 16;
-    // a chunk [m0, m1) holds the orders m0, m0 + ms, ... < m1 (ms = 1 but on the m-sharded route); m1 - 1 is its last order
-    const int m_end = pl->m_hi < 0 ? lmax + 1 : std::min(pl->m_hi, lmax + 1), ms = std::max(pl->m_step, 1);
-    for (int m0 = std::max(pl->m_lo, 0); m0 < m_end;) {
-        int last = m0;  // a chunk holds at least one m, whatever the budget
-        while (last + ms < m_end) {
-            const double bytes = f_per_m * ((last + ms - m0) / ms + 1) + (double)(prow[last + ms + 1] - prow[m0]) * pcol * sizeof(double);
-            if (bytes > budget) break;
-            last += ms;
-        }
-        const int m1 = last + 1;
-        chunks.emplace_back(m0, m1);
-        maxF = std::max(maxF, (size_t)(f_per_m * ((m1 - m0 + ms - 1) / ms)));
-        maxP = std::max(maxP, (size_t)(prow[m1] - prow[m0]) * pcol * sizeof(double));
-        m0 = last + ms;
-    }
-    HX_TRY(pl->F.alloc(maxF));
-    HX_TRY(pl->partial.alloc(maxP));
-    pl->last_chunks = (int)chunks.size();
+    HX_TRY(plan_m_chunks(pl, (double)pl->nrp_pad * analysis_f_rows(spin) * sh.ncol * sizeof(double), ts->arow, sweep_pcol(sh) * sizeof(double), chunks));
     for (auto &ch : chunks) {
         if (spin == 0)
-            HX_TRY(launch_chunk<0>(pl, ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
+            HX_TRY(launch_chunk<0>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
         else
-            HX_TRY(launch_chunk<2>(pl, ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
+            HX_TRY(launch_chunk<2>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
     }
     return HX_OK;
 }
@@ -1135,8 +1020,6 @@ int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 
 // A ring group of the Legendre kernel needs the rings of that group only -- of ALL maps of the sweep -- so the upload goes slab of rings
 // by slab of rings (ascending, poles first: the ring groups of an order then run in the order they always run in) and slab k's ring FFTs,
 // operand rows and the ring groups it completes are queued behind it.  What is left behind the last byte is 1 / nslab of one sweep.
-static hx_plan::TaskSet &stream_tasks(hx_plan *pl, int spin) { return spin ? pl->ts[3] : pl->ts[2]; }
-
 bool analysis_can_stream(hx_plan *pl, int spin, int nb)
 {
     if (!pl || pl->nside < 1 || pl->hsrc || pl->nssrc || pl->m_lo != 0 || pl->m_hi >= 0 || pl->m_step > 1) return false;
@@ -1166,9 +1049,9 @@ bool analysis_can_stream(hx_plan *pl, int spin, int nb)
 int analysis_stream_plan(hx_plan *pl, int spin, int nb, int nslab, StreamSweep &s)
 {
     if (!analysis_can_stream(pl, spin, nb)) return fail(HX_ERR_ARG, "analysis_stream_plan: not a streamable sweep");
-    if (spin) HX_TRY(ensure_rec2(pl));
-    HX_TRY(build_task_set(pl, spin, PipeCfg<2>::NW * (spin ? PipeCfg<2>::RBS : PipeCfg<0>::RBS), stream_tasks(pl, spin)));
-    hx_plan::TaskSet &ts = stream_tasks(pl, spin);
+    HX_TRY(spin_data(pl, spin, false, &s.sd));
+    HX_TRY(task_set(pl, spin, false, one_set_task_blocks(spin), &s.ts));
+    hx_plan::TaskSet &ts = *s.ts;
     const SweepShape sh = sweep_shape(spin, nb);
     s.pl = pl; s.spin = spin; s.nb = nb;
     // slab edges: whole 32-ring-pair blocks, about equal numbers of pixels (a ring pair is 8 nsub pixels, the equator ring 4)
@@ -1216,7 +1099,7 @@ int analysis_stream_start(StreamSweep &s)
     hx_plan *pl = s.pl;
     const SweepShape sh = sweep_shape(s.spin, s.nb);
     // the accumulation rows start at zero: every ring group adds
-    HX_HIP(hipMemsetAsync(pl->partial.p, 0, (size_t)stream_tasks(pl, s.spin).arow[pl->lmax + 1] * sweep_pcol(sh) * sizeof(double), rt().stream));
+    HX_HIP(hipMemsetAsync(pl->partial.p, 0, (size_t)s.ts->arow[pl->lmax + 1] * sweep_pcol(sh) * sizeof(double), rt().stream));
     pl->last_chunks = 1;
     return HX_OK;
 }
@@ -1225,7 +1108,7 @@ template <int SPIN>
 static int stream_slab(StreamSweep &s, int k)
 {
     hx_plan *pl = s.pl;
-    hx_plan::TaskSet &ts = stream_tasks(pl, SPIN);
+    hx_plan::TaskSet &ts = *s.ts;
     const SweepShape sh = sweep_shape(SPIN, s.nb);
     const int ng = sh.ng + (sh.nbx > 0 ? 1 : 0), lmax = pl->lmax, nm = lmax + 1;
     const int rp_lo = s.rp_edge[k], rp_hi = s.rp_edge[k + 1];
@@ -1246,7 +1129,7 @@ static int stream_slab(StreamSweep &s, int k)
         A.P = P; A.tasks = ts.d_tasks.as<LegTask>(); A.F = pl->F.as<double>(); A.partial = pl->partial.as<double>();
         A.m0 = 0; A.ms = 1; A.row0 = 0; A.ng = ng; A.ncol = sh.ncol; A.pcol = sweep_pcol(sh);
         A.of_m = s.d_of_m.as<MTasks>() + (size_t)k * (lmax + 1); A.arow = ts.d_arow.as<long long>(); A.arow0 = 0; A.add_all = 1;
-        HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>()));
+        HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, s.sd->cn.as<double2>()));
     }
     HX_HIP(hipGetLastError());
     return HX_OK;
@@ -1261,18 +1144,20 @@ int analysis_stream_slab(StreamSweep &s, int k)
 int analysis_stream_end(StreamSweep &s)
 {
     hx_plan *pl = s.pl;
-    hx_plan::TaskSet &ts = stream_tasks(pl, s.spin);
     const SweepShape sh = sweep_shape(s.spin, s.nb);
-    const int ng = sh.ng + (sh.nbx > 0 ? 1 : 0), nm = pl->lmax + 1, pcol = sweep_pcol(sh);
-    PlanDev P = pl->dev();
     ProfScope ps("alm_reduce");
-    if (s.spin == 0)
-        hipLaunchKernelGGL(k_alm_reduce<0>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->partial.as<double>(),
-                           0LL, 0, 1, s.nb, ng, pcol, s.d_fl, 0, s.d_alms, pl->nlm, ts.d_arow.as<long long>(), pl->al0.as<double>());
-    else
-        hipLaunchKernelGGL(k_alm_reduce<2>, dim3(nm), dim3(256), 0, rt().stream, P, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->partial.as<double>(),
-                           0LL, 0, 1, s.nb, ng, pcol, s.d_fl, 0, s.d_alms, pl->nlm, ts.d_arow.as<long long>(), pl->al2.as<double>());
+    launch_alm_reduce(pl, s.spin, *s.ts, 0LL, 0, 1, pl->lmax + 1, s.nb, sh.ng + (sh.nbx > 0 ? 1 : 0), sweep_pcol(sh), s.d_fl, 0, s.d_alms, s.sd->al.as<double>());
     HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
+// (wave, 32-l block) pairs of one sweep over the task list the flop figures are quoted on (flop_task_blocks)
+static int flop_wave_blocks(hx_plan *pl, int spin, double *out)
+{
+    hx_plan::TaskSet *ts = nullptr;
+    HX_TRY(task_set(pl, spin, false, flop_task_blocks(spin), &ts));
+    *out = 0.0;
+    for (const LegTask &t : ts->tasks) *out += (double)t.nrb * ((pl->lmax - std::max(t.m, spin)) / LBLK + 1);
     return HX_OK;
 }
 
@@ -1287,14 +1172,9 @@ extern "C" int hx_plan_mfma_flops(hx_plan *pl, int spin, int ncomp, double *flop
     using namespace hx;
     if (!pl || !flops || ncomp < 1 || (spin != 0 && spin != 2)) return fail(HX_ERR_ARG, "hx_plan_mfma_flops: bad arguments");
     HX_TRY(ensure_ready());
-    HX_TRY(build_tasks(pl, spin));
-    const hx_plan::TaskSet &ts = pl->ts[spin ? 1 : 0];
-    const int nop = spin ? 2 : 1, l0min = spin ? 2 : 0;
     double wave_blocks = 0.0;
-    for (const LegTask &t : ts.tasks) {
-        const int l0 = std::max(t.m, l0min);
-        wave_blocks += (double)t.nrb * ((pl->lmax - l0) / LBLK + 1);
-    }
+    HX_TRY(flop_wave_blocks(pl, spin, &wave_blocks));
+    const int nop = spin ? 2 : 1;
     double per_wave_block = 0.0;
     for (int c0 = 0, nb = 0; c0 < ncomp; c0 += nb) {
         nb = analysis_next_batch(spin, ncomp - c0);
@@ -1334,13 +1214,9 @@ extern "C" int hx_plan_executed_flops(hx_plan *pl, int spin, int ncomp, double *
     using namespace hx;
     if (!out2) return fail(HX_ERR_ARG, "hx_plan_executed_flops: null output");
     HX_TRY(hx_plan_mfma_flops(pl, spin, ncomp, &out2[0]));
-    const hx_plan::TaskSet &ts = pl->ts[spin ? 1 : 0];
-    const int nop = spin ? 2 : 1, l0min = spin ? 2 : 0;
     double wave_blocks = 0.0;
-    for (const LegTask &t : ts.tasks) {
-        const int l0 = std::max(t.m, l0min);
-        wave_blocks += (double)t.nrb * ((pl->lmax - l0) / LBLK + 1);
-    }
+    HX_TRY(flop_wave_blocks(pl, spin, &wave_blocks));
+    const int nop = spin ? 2 : 1;
     int sweeps = 0;
     for (int c0 = 0, nb = 0; c0 < ncomp; c0 += nb, ++sweeps) nb = analysis_next_batch(spin, ncomp - c0);
     out2[1] = wave_blocks * sweeps * (double)RBLK * LBLK * nop * 4.0;

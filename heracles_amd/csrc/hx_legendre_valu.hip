@@ -53,7 +53,7 @@ __device__ unsigned long long g_valu_flops;
 struct ValuParams {
     PlanDev P;
     const LegTask *__restrict__ tasks;  // tasks [t0, t1) of the m-chunk
-    const double *__restrict__ kfs;     // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinSet::kf)
+    const double *__restrict__ kfs;     // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinData::kf)
     int s;
     const double *__restrict__ F;       // [(m - m0) / ms][rp][NF]
     double *__restrict__ partial;       // [row - row0][NA]
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(64, VALU_WAVES) void k_legendre_valu(ValuParams A, 
 //   spin 2: P+_N = sum lambda+ a+,  P-_S = sum (-1)^(l+m) lambda+ a-,  P-_N = sum lambda- a-,  P+_S = sum (-1)^(l+m) lambda- a+,
 //           a+- = -(E +- iB);  Q = (P+ + P-) / 2,  U = (P+ - P-) / 2i.
 //   spin s (SPIN_ANY, one field per sweep): as spin 2 with lambda+- of weight +-s from l0 = max(m, s) -- seeds from spin_seeds, tables
-//           of hx_plan::SpinSet -- and a+ = -(E + iB), a- = -(-1)^s (E - iB): the sign of an odd s is applied where alpha_l a_lm is
+//           of hx_plan::SpinData -- and a+ = -(E + iB), a- = -(-1)^s (E - iB): the sign of an odd s is applied where alpha_l a_lm is
 //           formed, everything downstream is the spin-2 code.
 // Every accumulator belongs to ONE chain.  A scaled chain (exponent < 0) is not masked inside the loop: what it adds between two
 // checks is dropped at the next check (its accumulators are zeroed as long as it is not live: it has never contributed before),
@@ -461,7 +461,7 @@ struct SynValuParams {
     const LegTask *__restrict__ tasks;
     const double2 *__restrict__ alm;  // component c at + c alm_stride: spin 0: the maps' alms; spin 2: (E, B) per field
     long long alm_stride;
-    const double *__restrict__ kfs;   // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinSet::kf)
+    const double *__restrict__ kfs;   // SPIN_ANY: seed factors of spin weight s (hx_plan::SpinData::kf)
     int s;
     double *__restrict__ Fv;          // [m][rp][NV]: component c = (N_re, N_im, S_re, S_im) at 4 c (spin 2: Q, U of field b at 8 b)
 };
@@ -739,38 +739,31 @@ __global__ __launch_bounds__(64, (SPIN == 0 && NB == 4) ? 2 : VALU_WAVES) void k
 // Fv of `units` maps (spin 0: 1, 2 or 4) / fields (spin 2: 1 or 2) whose alms start at d_alm; ts = the task set of
 // synth_valu_task_blocks(spin, units) ring blocks per task; rings outside the task list (pruned) stay zero
 template <int SPIN, int NB>
-static int launch_synth_valu_t(hx_plan *pl, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, int s)
+static int launch_synth_valu_t(hx_plan *pl, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, int s)
 {
     hipStream_t st = rt().stream;
     constexpr int NV = SynValuCfg<SPIN, NB>::NV;
     HX_HIP(hipMemsetAsync(d_Fv, 0, sizeof(double) * (size_t)(pl->lmax + 1) * pl->nrp_pad * NV, st));
     SynValuParams A;
     A.P = pl->dev(); A.tasks = ts.d_tasks.as<LegTask>(); A.alm = d_alm; A.alm_stride = pl->nlm; A.Fv = d_Fv;
-    A.kfs = nullptr; A.s = s;
-    const double2 *cn = SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
-    const double *al = SPIN == 0 ? pl->al0.as<double>() : pl->al2.as<double>();
-    if (SPIN == SPIN_ANY) {  // tables and seed factors of this weight: never those of spin 2
-        hx_plan::SpinSet *set = nullptr;
-        HX_TRY(ensure_rec_s(pl, s, &set));
-        A.kfs = set->kf.as<double>(); cn = set->cn.as<double2>(); al = set->al.as<double>();
-    }
+    A.kfs = sd.kf.as<double>(); A.s = s;  // (kf: null but for SPIN_ANY)
     ProfScope ps("legendre_synthesis");
     ProfScope ps2("legendre_synth_valu");
-    hipLaunchKernelGGL((k_legendre_synth_valu<SPIN, NB>), dim3((unsigned)ts.tasks.size()), dim3(64), 0, st, A, cn, al);
+    hipLaunchKernelGGL((k_legendre_synth_valu<SPIN, NB>), dim3((unsigned)ts.tasks.size()), dim3(64), 0, st, A, sd.cn.as<double2>(), sd.al.as<double>());
     HX_HIP(hipGetLastError());
     return HX_OK;
 }
-int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic)
+int launch_synth_valu(hx_plan *pl, int spin, int units, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic)
 {
-    if (generic) {  // ts: the task set of valu_tasks(pl, spin, ., ., true)
-        if (spin >= 1 && spin <= pl->lmax && units == 1) return launch_synth_valu_t<SPIN_ANY, 1>(pl, ts, d_alm, d_Fv, spin);
+    if (generic) {  // sd, ts: those of the run-time-spin family of this weight
+        if (spin >= 1 && spin <= pl->lmax && units == 1) return launch_synth_valu_t<SPIN_ANY, 1>(pl, sd, ts, d_alm, d_Fv, spin);
         return fail(HX_ERR_ARG, "launch_synth_valu: %d units of spin %d on the run-time-spin sweep", units, spin);
     }
-    if (spin == 0 && units == 1) return launch_synth_valu_t<0, 1>(pl, ts, d_alm, d_Fv, 0);
-    if (spin == 0 && units == 2) return launch_synth_valu_t<0, 2>(pl, ts, d_alm, d_Fv, 0);
-    if (spin == 0 && units == 4) return launch_synth_valu_t<0, 4>(pl, ts, d_alm, d_Fv, 0);
-    if (spin == 2 && units == 1) return launch_synth_valu_t<2, 1>(pl, ts, d_alm, d_Fv, 2);
-    if (spin == 2 && units == 2) return launch_synth_valu_t<2, 2>(pl, ts, d_alm, d_Fv, 2);
+    if (spin == 0 && units == 1) return launch_synth_valu_t<0, 1>(pl, sd, ts, d_alm, d_Fv, 0);
+    if (spin == 0 && units == 2) return launch_synth_valu_t<0, 2>(pl, sd, ts, d_alm, d_Fv, 0);
+    if (spin == 0 && units == 4) return launch_synth_valu_t<0, 4>(pl, sd, ts, d_alm, d_Fv, 0);
+    if (spin == 2 && units == 1) return launch_synth_valu_t<2, 1>(pl, sd, ts, d_alm, d_Fv, 2);
+    if (spin == 2 && units == 2) return launch_synth_valu_t<2, 2>(pl, sd, ts, d_alm, d_Fv, 2);
     return fail(HX_ERR_ARG, "launch_synth_valu: %d units of spin %d", units, spin);
 }
 
@@ -778,7 +771,7 @@ int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, co
 // host: one m-chunk of one map / field
 // =====================================================================================
 template <int SPIN>
-static int launch_valu_chunk_t(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, int s)
+static int launch_valu_chunk_t(hx_plan *pl, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, int s)
 {
     hipStream_t st = rt().stream;
     PlanDev P = pl->dev();
@@ -798,15 +791,8 @@ static int launch_valu_chunk_t(hx_plan *pl, hx_plan::TaskSet &ts, int m0, int m1
         ValuParams A;
         A.P = P; A.tasks = ts.d_tasks.as<LegTask>() + t0; A.F = pl->F.as<double>(); A.partial = pl->partial.as<double>();
         A.m0 = m0; A.ms = ms; A.row0 = ts.rows_before_m[m0];
-        A.kfs = nullptr; A.s = s;
-        const double2 *cn = SPIN == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
-        const double *al = SPIN == 0 ? pl->al0.as<double>() : pl->al2.as<double>();
-        if (SPIN == SPIN_ANY) {
-            hx_plan::SpinSet *set = nullptr;
-            HX_TRY(ensure_rec_s(pl, s, &set));
-            A.kfs = set->kf.as<double>(); cn = set->cn.as<double2>(); al = set->al.as<double>();
-        }
-        hipLaunchKernelGGL(k_legendre_valu<SPIN>, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, A, cn, al);
+        A.kfs = sd.kf.as<double>(); A.s = s;  // (kf: null but for SPIN_ANY)
+        hipLaunchKernelGGL(k_legendre_valu<SPIN>, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, A, sd.cn.as<double2>(), sd.al.as<double>());
     }
     HX_HIP(hipGetLastError());
     return HX_OK;
@@ -820,10 +806,10 @@ int valu_exec_flops(unsigned long long *v, bool reset)
     return HX_OK;
 }
 
-int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic)
+int launch_valu_chunk(hx_plan *pl, int spin, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic)
 {
-    if (generic) return launch_valu_chunk_t<SPIN_ANY>(pl, ts, m0, m1, c0, d_rw, spin);
-    return spin == 0 ? launch_valu_chunk_t<0>(pl, ts, m0, m1, c0, d_rw, 0) : launch_valu_chunk_t<2>(pl, ts, m0, m1, c0, d_rw, 2);
+    if (generic) return launch_valu_chunk_t<SPIN_ANY>(pl, sd, ts, m0, m1, c0, d_rw, spin);
+    return spin == 0 ? launch_valu_chunk_t<0>(pl, sd, ts, m0, m1, c0, d_rw, 0) : launch_valu_chunk_t<2>(pl, sd, ts, m0, m1, c0, d_rw, 2);
 }
 
 }  // namespace hx

@@ -72,9 +72,9 @@ extern "C" int hx_ring_modes(hx_plan *pl, int ncomp, const double *maps, const d
         HX_TRY(check_orders(pl, m_first[q], m_count[q], m_step, "hx_ring_modes"));
         if (m_count[q] > 0 && (!outs[q] || !is_device_ptr(outs[q]))) return fail(HX_ERR_ARG, "hx_ring_modes: outputs must be device buffers");
     }
-    HX_TRY(build_tasks(pl, 0));
-    HX_TRY(build_tasks(pl, 2));
-    const hx_plan::TaskSet &ts = pl->ts[0], &ts2 = pl->ts[1];
+    hx_plan::TaskSet *ts = nullptr, *ts2 = nullptr;  // (k_ring_modes reads the first ring block of every order only: any block count would do)
+    HX_TRY(task_set(pl, 0, false, flop_task_blocks(0), &ts));
+    HX_TRY(task_set(pl, 2, false, flop_task_blocks(2), &ts2));
     InView vmaps, vrw, vpw;
     HX_TRY(vmaps.bind(maps, sizeof(double) * (size_t)ncomp * pl->npix));
     HX_TRY(vrw.bind(ring_weights, sizeof(double) * pl->nrp));
@@ -93,7 +93,7 @@ extern "C" int hx_ring_modes(hx_plan *pl, int ncomp, const double *maps, const d
             if (m_count[q] <= 0) continue;
             dim3 grid(m_count[q], (pl->nrp_pad + 255) / 256);
             hipLaunchKernelGGL(k_ring_modes, grid, dim3(256), 0, rt().stream, P, pl->Y.as<double2>(), nb, c0, m_first[q], m_count[q], m_step,
-                               vrw.as<double>(), ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), ts2.d_tasks.as<LegTask>(), ts2.d_of_m.as<MTasks>(),
+                               vrw.as<double>(), ts->d_tasks.as<LegTask>(), ts->d_of_m.as<MTasks>(), ts2->d_tasks.as<LegTask>(), ts2->d_of_m.as<MTasks>(),
                                reinterpret_cast<double4 *>(outs[q]));
         }
         HX_HIP(hipGetLastError());

@@ -151,14 +151,8 @@ static int plan_tables(hx_plan *pl)
     HX_TRY(upload(pl->tw, tw));
     HX_TRY(upload(pl->mfac, mfac));
     HX_TRY(upload(pl->kfac2, kfac2));
-    hipStream_t st = rt().stream;
-    HX_TRY(pl->cn0.alloc(sizeof(double2) * (pl->nlm + TABLE_PAD)));
-    HX_TRY(pl->al0.alloc(sizeof(double) * (pl->nlm + TABLE_PAD)));
-    HX_HIP(hipMemsetAsync(pl->cn0.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), st));
-    HX_HIP(hipMemsetAsync(pl->al0.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), st));
-    hipLaunchKernelGGL(k_init_norm0, dim3((2 * (lmax + 1) + 63) / 64), dim3(64), 0, st, lmax, pl->cn0.as<double2>(), pl->al0.as<double>());
-    HX_HIP(hipGetLastError());
-    return HX_OK;
+    hx_plan::SpinData *sd = nullptr;
+    return spin_data(pl, 0, false, &sd);  // (the spin-0 tables are part of every plan)
 }
 
 extern "C" hx_plan *hx_plan_create(int nside, int lmax, int max_comp)
@@ -278,37 +272,28 @@ extern "C" int64_t hx_plan_scratch_bytes(const hx_plan *pl)
 {
     if (!pl) return 0;
     size_t spin_tables = 0;
-    for (const auto &kv : pl->spin_sets) spin_tables += kv.second.cn.bytes + kv.second.al.bytes;
-    return (int64_t)(pl->stage[0].bytes + pl->stage[1].bytes + pl->stage[2].bytes + pl->resid_maps.bytes + pl->Y.bytes + pl->F.bytes + pl->partial.bytes + pl->rec0.bytes + pl->rec2.bytes + pl->cn0.bytes + pl->al0.bytes + pl->cn2.bytes + pl->al2.bytes +
+    for (const auto &kv : pl->spins) spin_tables += kv.second.cn.bytes + kv.second.al.bytes;
+    return (int64_t)(pl->stage[0].bytes + pl->stage[1].bytes + pl->stage[2].bytes + pl->resid_maps.bytes + pl->Y.bytes + pl->F.bytes + pl->partial.bytes +
                      pl->bhat.bytes + pl->syn_tab.bytes + spin_tables);
 }
 
 extern "C" int hx_plan_last_chunks(const hx_plan *pl) { return pl ? pl->last_chunks : 0; }
 
+// =====================================================================================
+// per-spin state: recursion tables, seed factors, task sets
+// =====================================================================================
 namespace hx {
-int ensure_rec2(hx_plan *pl)
+int spin_data(hx_plan *pl, int spin, bool generic, hx_plan::SpinData **out)
 {
-    if (pl->cn2.p) return HX_OK;
-    HX_TRY(pl->cn2.alloc(sizeof(double2) * (pl->nlm + TABLE_PAD)));
-    HX_TRY(pl->al2.alloc(sizeof(double) * (pl->nlm + TABLE_PAD)));
-    HX_HIP(hipMemsetAsync(pl->cn2.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), rt().stream));
-    HX_HIP(hipMemsetAsync(pl->al2.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), rt().stream));
-    hipLaunchKernelGGL(k_init_norm2, dim3((pl->lmax + 64) / 64), dim3(64), 0, rt().stream, pl->lmax, pl->cn2.as<double2>(), pl->al2.as<double>());
-    HX_HIP(hipGetLastError());
-    return HX_OK;
-}
-
-int ensure_rec_s(hx_plan *pl, int s, hx_plan::SpinSet **out)
-{
-    const int lmax = pl->lmax;
-    if (s < 1 || s > lmax) return fail(HX_ERR_ARG, "ensure_rec_s: spin %d at lmax %d", s, lmax);
-    hx_plan::SpinSet &set = pl->spin_sets[s];
-    *out = &set;
-    if (set.cn.p && set.al.p && set.kf.p) return HX_OK;
-    // seed factors of spin_seeds, by incremental products like kfac2 (upwards and downwards from m = s, where the factorial ratio is 1):
-    //   m >= s: (-1)^m sqrt((2m+1)/4pi) sqrt((2m)!/((m+s)!(m-s)!)) 2^-(m-s);   m < s: sqrt((2s+1)/4pi) sqrt((2s)!/((s+m)!(s-m)!)) 2^-(s-m)
-    std::vector<double> kf(lmax + 1);
-    {
+    const int lmax = pl->lmax, s = spin;
+    if (generic ? (s < 1 || s > lmax) : (s != 0 && s != 2)) return fail(HX_ERR_ARG, "spin_data: spin %d at lmax %d", s, lmax);
+    hx_plan::SpinData &sd = pl->spins[{s, generic}];
+    *out = &sd;
+    if (sd.cn.p && sd.al.p && (sd.kf.p || !generic)) return HX_OK;
+    if (generic) {
+        // seed factors of spin_seeds, by incremental products like kfac2 (upwards and downwards from m = s, where the factorial ratio is 1):
+        //   m >= s: (-1)^m sqrt((2m+1)/4pi) sqrt((2m)!/((m+s)!(m-s)!)) 2^-(m-s);   m < s: sqrt((2s+1)/4pi) sqrt((2s)!/((s+m)!(s-m)!)) 2^-(s-m)
+        std::vector<double> kf(lmax + 1);
         const long double fourpi = 4.0L * 3.141592653589793238462643383279502884L;
         long double k = 1.0L;
         for (int m = s; m <= lmax; ++m) {
@@ -321,16 +306,106 @@ int ensure_rec_s(hx_plan *pl, int s, hx_plan::SpinSet **out)
             k *= sqrtl((long double)(s + m + 1) / (s - m)) / 2.0L;
             kf[m] = (double)k;
         }
+        for (double v : kf)
+            if (!std::isfinite(v)) return fail(HX_ERR_UNSUPPORTED, "spin-%d values: the seeds of the recursion leave the range of a double", s);
+        HX_TRY(upload(sd.kf, kf));
     }
-    for (double v : kf)
-        if (!std::isfinite(v)) return fail(HX_ERR_UNSUPPORTED, "spin-%d values: the seeds of the recursion leave the range of a double", s);
-    HX_TRY(upload(set.kf, kf));
-    HX_TRY(set.cn.alloc(sizeof(double2) * (pl->nlm + TABLE_PAD)));
-    HX_TRY(set.al.alloc(sizeof(double) * (pl->nlm + TABLE_PAD)));
-    HX_HIP(hipMemsetAsync(set.cn.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), rt().stream));
-    HX_HIP(hipMemsetAsync(set.al.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), rt().stream));
-    hipLaunchKernelGGL(k_init_norm_s, dim3((lmax + 64) / 64), dim3(64), 0, rt().stream, lmax, s, set.cn.as<double2>(), set.al.as<double>());
+    hipStream_t st = rt().stream;
+    HX_TRY(sd.cn.alloc(sizeof(double2) * (pl->nlm + TABLE_PAD)));
+    HX_TRY(sd.al.alloc(sizeof(double) * (pl->nlm + TABLE_PAD)));
+    HX_HIP(hipMemsetAsync(sd.cn.p, 0, sizeof(double2) * (pl->nlm + TABLE_PAD), st));
+    HX_HIP(hipMemsetAsync(sd.al.p, 0, sizeof(double) * (pl->nlm + TABLE_PAD), st));
+    double2 *cn = sd.cn.as<double2>();
+    double *al = sd.al.as<double>();
+    if (generic) hipLaunchKernelGGL(k_init_norm_s, dim3((lmax + 64) / 64), dim3(64), 0, st, lmax, s, cn, al);
+    else if (s == 2) hipLaunchKernelGGL(k_init_norm2, dim3((lmax + 64) / 64), dim3(64), 0, st, lmax, cn, al);
+    else hipLaunchKernelGGL(k_init_norm0, dim3((2 * (lmax + 1) + 63) / 64), dim3(64), 0, st, lmax, cn, al);
     HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
+// libsharp's published heuristic for the largest m that contributes on a ring
+// (sharp_get_mlim): rings with m > mlim are skipped.
+static int ring_mlim(int lmax, int spin, double sth, double cth)
+{
+    double ofs = lmax * 0.01;
+    if (ofs < 100.) ofs = 100.;
+    double b = -2 * spin * fabs(cth);
+    double t1 = lmax * sth + ofs;
+    double c = (double)spin * spin - t1 * t1;
+    double discr = b * b - 4 * c;
+    if (discr <= 0) return lmax;
+    double res = (-b + sqrt(discr)) / 2.;
+    if (res > lmax) res = lmax;
+    return (int)(res + 0.5);
+}
+
+// The task set of `blocks` ring blocks per task of a spin weight and family, built and uploaded when it is first asked for (the tables are
+// not: the flop accounting and hx_ring_modes read task sets only).  Which kernel wants which block count is the kernels' business:
+// valu_task_blocks, synth_valu_task_blocks (hx_legendre_valu.hip), one_set_task_blocks, flop_task_blocks (hx_analysis.hip).
+int task_set(hx_plan *pl, int spin, bool generic, int blocks, hx_plan::TaskSet **out)
+{
+    if (spin < 0 || blocks < 1) return fail(HX_ERR_ARG, "task_set: %d ring blocks per task of spin %d", blocks, spin);
+    std::map<int, hx_plan::TaskSet> &store = pl->spins[{spin, generic}].tasks;
+    const auto it = store.find(blocks);
+    if (it != store.end()) {
+        *out = &it->second;
+        return HX_OK;
+    }
+    hx_plan::TaskSet &ts = store[blocks];
+    const int lmax = pl->lmax;
+    const int nrb = (pl->nrp + RBLK - 1) / RBLK;
+    ts.of_m.assign(lmax + 1, MTasks{0, 0});
+    ts.rows_before_m.assign(lmax + 2, 0);
+    ts.arow.assign(lmax + 2, 0);
+    long long rows = 0, arows = 0;
+    // mlim is monotone in the ring index (pole -> equator): first active ring by bisection
+    std::vector<int> mlim(pl->nrp);
+    for (int rp = 0; rp < pl->nrp; ++rp) mlim[rp] = ring_mlim(lmax, spin, pl->h_sth[rp], pl->h_z[rp]);
+    for (int m = 0; m <= lmax; ++m) {
+        ts.rows_before_m[m] = rows;
+        ts.arow[m] = arows;
+        const int l0 = std::max(m, spin);
+        if (l0 <= lmax) arows += (long long)LBLK * ((lmax - l0) / LBLK + 1);
+        ts.of_m[m].first = (int)ts.tasks.size();
+        if (l0 <= lmax) {
+            int first = (int)(std::lower_bound(mlim.begin(), mlim.end(), m) - mlim.begin());
+            if (first >= pl->nrp) first = pl->nrp - 1;
+            for (int rb = first / RBLK; rb < nrb; rb += blocks) {
+                LegTask t;
+                t.m = m; t.rb0 = rb; t.nrb = std::min(blocks, nrb - rb); t.pad = 0; t.pout = rows;
+                rows += (long long)LBLK * ((lmax - l0) / LBLK + 1);  // padded to whole 32-l blocks (the pipelined kernel stores unconditionally)
+                ts.tasks.push_back(t);
+            }
+        }
+        ts.of_m[m].count = (int)ts.tasks.size() - ts.of_m[m].first;
+    }
+    ts.rows_before_m[lmax + 1] = rows;
+    ts.arow[lmax + 1] = arows;
+    int rc = upload(ts.d_tasks, ts.tasks);
+    if (rc == HX_OK) rc = upload(ts.d_of_m, ts.of_m);
+    if (rc == HX_OK) rc = upload(ts.d_arow, ts.arow);
+    if (rc != HX_OK) store.erase(blocks);  // (only a complete set stays in the store)
+    *out = rc == HX_OK ? &ts : nullptr;
+    return rc;
+}
+
+// The highest order every ring pair is synthesised for by the batched synthesis: the tasks of an order m start at the 32-ring-pair block
+// that holds the first ring with mlim >= m (task_set), so ring pair rp is covered for m <= the largest mlim of its block; the rows beyond
+// are never written and the spectrum pass does not read them (no 32 GB memset per sweep of ten fields)
+int synth_mlim(hx_plan *pl, int spin, const int **mlim)
+{
+    hx_plan::SpinData *sd = nullptr;
+    HX_TRY(spin_data(pl, spin, false, &sd));
+    if (!sd->syn_mlim.p) {
+        std::vector<int> h(pl->nrp_pad, -1);
+        for (int rp = 0; rp < pl->nrp; ++rp) {
+            const int last = std::min(rp / RBLK * RBLK + RBLK - 1, pl->nrp - 1);
+            h[rp] = std::min(pl->lmax, ring_mlim(pl->lmax, spin, pl->h_sth[last], pl->h_z[last]));
+        }
+        HX_TRY(upload(sd->syn_mlim, h));
+    }
+    *mlim = sd->syn_mlim.as<int>();
     return HX_OK;
 }
 }  // namespace hx

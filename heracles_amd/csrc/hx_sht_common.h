@@ -179,7 +179,7 @@ __device__ inline void spin2_seeds(int m, double sth, double omx, double kfac2m,
 // sh = sin(theta/2), ch = cos(theta/2), N_l = sqrt((2l+1)/4pi):
 //   m >= s:  (-1)^m N_m sqrt((2m)!/((m+s)!(m-s)!)) (sh ch)^(m-s)  x  sh^(2s) (+s) / ch^(2s) (-s)
 //   m <  s:  N_s sqrt((2s)!/((s+m)!(s-m)!)) (sh ch)^(s-m)  x  (-1)^m sh^(2m) (+s) / (-1)^s ch^(2m) (-s)
-// kfsm = the factor in front of the powers x 2^-|m-s| (sh ch = sin(theta) / 2), for m >= s with its sign: hx_plan::SpinSet::kf.
+// kfsm = the factor in front of the powers x 2^-|m-s| (sh ch = sin(theta) / 2), for m >= s with its sign: hx_plan::SpinData::kf.
 // At s = 2 these are spin2_seeds.
 __device__ inline void spin_seeds(int s, int m, double sth, double omx, double kfsm, SVal &sp, SVal &sm)
 {
@@ -368,35 +368,36 @@ struct hx_plan {
     int m_lo = 0, m_hi = -1, m_step = 1;
     long long npix = 0, ny = 0, nlm = 0;
     size_t lds_fft = 0;
-    hx::DevBuf z, omz, sth, rwdef, nsub, shifted, startN, startS, bhat_off, tw, bhat, mfac, kfac2, rec0, rec2, cn0, al0, cn2, al2;
+    hx::DevBuf z, omz, sth, rwdef, nsub, shifted, startN, startS, bhat_off, tw, bhat, mfac, kfac2;
     std::vector<double> h_sth, h_z;
     std::vector<int> h_nsub;
     std::vector<long long> h_startN, h_startS;   // first pixel of the northern / southern ring of a pair (-1: the equator has no southern ring)
+    // the ring groups of every order for one number of 32-ring-pair blocks per task, pruned by ring_mlim(lmax, spin)
     struct TaskSet {
-        bool built = false;
         std::vector<hx::LegTask> tasks;       // ordered by m; tasks of one m contiguous
         std::vector<hx::MTasks> of_m;
         std::vector<long long> rows_before_m; // partial rows of all tasks with smaller m (size lmax+2)
         std::vector<long long> arow;          // the same with ONE span of rows per m (pipelined kernel: ring groups summed in place)
         hx::DevBuf d_tasks, d_of_m, d_arow;
-    } ts[8];  // spin 0, spin 2, spin 0 with half-size work-groups, spin 2 with one ring set per wave (4 ring blocks per task),
-       // spin 2 / spin 0 on the vector unit (hx_legendre_valu.hip: 2 R ring blocks per task), spin 2 / spin 0 synthesis of several
-       // maps per sweep (8 ring blocks per task)
-    // what the vector-unit sweeps of a spin weight other than 0 and 2 need (analysis and synthesis), built on first use and kept per
-    // weight: coefficients and scalings of its recursion (k_init_norm_s), seed factors (spin_seeds), tasks pruned by ring_mlim(lmax, s)
-    struct SpinSet {
-        hx::DevBuf cn, al, kf;
-        TaskSet ts;
     };
-    std::map<int, SpinSet> spin_sets;
+    // What the Legendre sweeps of one spin weight need of a plan, per kernel family: the kernels specialised for spin 0 / spin 2 (their
+    // seed factors are mfac / kfac2 above; tables of k_init_norm0 / k_init_norm2) and the run-time-spin sweeps of the vector unit (any
+    // weight >= 1; tables of k_init_norm_s and the seed factors kf of spin_seeds).  Spin 2 has one of each: they share nothing.
+    // spin_data() hands one out and fills the tables on first use, task_set() its task sets (hx_plan.hip).
+    struct SpinData {
+        hx::DevBuf cn, al, kf;       // coefficients and scalings of the normalised recursion [nlm + TABLE_PAD]; seed factors [lmax + 1] (run-time spin only)
+        hx::DevBuf syn_mlim;         // batched synthesis: per ring pair the highest m its rows of Fv are written for (synth_mlim(), hx_plan.hip)
+        hx::DevBuf syn_boff;         // batched synthesis: first B-operand table block of every m (launch_synth_duo)
+        std::map<int, TaskSet> tasks;  // by 32-ring-pair blocks per task: a set is a function of (plan, spin weight, blocks) only
+    };
+    std::map<std::pair<int, bool>, SpinData> spins;  // by (spin weight, run-time-spin family)
     struct FftClass { int M, first, count, big; };
     std::vector<FftClass> fft_classes;   // ring pairs grouped by in-LDS FFT length
     hx::DevBuf fft_rp_list;
     hx::DevBuf fft_desc;                 // RingDesc of every entry of fft_rp_list (one 32-byte read per work item instead of two dependent ones)
     std::vector<int> h_fft_rp_list;      // (host copy: ring pairs in DESCENDING order within a class)
     hx::DevBuf Y, F, partial, d_dbg, resid_maps, pw_sym;  // (F doubles as the scratch of a synthesis: ring modes + ring spectra)
-    hx::DevBuf syn_mlim0, syn_mlim2;  // per ring pair: the highest m its rows of Fv are written for (task pruning by blocks of 32 ring pairs)
-    hx::DevBuf syn_tab, syn_boff0, syn_boff2;  // batched synthesis on the matrix unit (hx_synth_duo.hip): B-operand table of a sweep, first table block of every m
+    hx::DevBuf syn_tab;  // batched synthesis on the matrix unit (hx_synth_duo.hip): B-operand table of a sweep
     const double *pw_checked = nullptr;       // the pixel-weight array of the current call that pw_mode describes
     int pw_mode = 0;                          // 1: one weight per pixel; 2: the array repeats over the quadrants of every ring and from north to south (healpy's weights)
     static constexpr int NSTAGE = 3;          // staging buffers of the upload pipeline (hx_map2alm_multi / _list; hx_map2alm of host maps is one job of it)
@@ -410,8 +411,10 @@ struct hx_plan {
 namespace hx {
 // hx_plan.hip
 hx_plan *plan_create_equiangular(int N, int lmax);
-int ensure_rec2(hx_plan *pl);
-int ensure_rec_s(hx_plan *pl, int s, hx_plan::SpinSet **set);  // tables of pl->spin_sets[s] (1 <= s <= lmax)
+// per-spin state of a plan, built on first use.  generic: the run-time-spin family (1 <= spin <= lmax), else the kernels of spin 0 / spin 2
+int spin_data(hx_plan *pl, int spin, bool generic, hx_plan::SpinData **out);             // with its tables (filled on the library stream)
+int task_set(hx_plan *pl, int spin, bool generic, int blocks, hx_plan::TaskSet **out);   // tasks of `blocks` ring blocks each
+int synth_mlim(hx_plan *pl, int spin, const int **mlim);                                 // SpinData::syn_mlim of the specialised family
 // hx_ring_fft.hip
 int ring_fft_plan_init(hx_plan *pl, const std::vector<int> &nsub, const std::vector<long long> &sN, const std::vector<long long> &sS);  // (hx_plan_create, behind the band-limit tables)
 int launch_ring_subdft_maps(hx_plan *pl, int nb, const double *d_maps, const double *d_pw, double2 *Y, int rp_lo = 0, int rp_hi = 0x7fffffff);  // ring pairs [rp_lo, rp_hi) only
@@ -422,7 +425,8 @@ int synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, double
 // hx_map2alm.hip
 int check_sht_args(hx_plan *pl, int spin, int ncomp, const void *a, const void *b, bool any_spin = false);  // any_spin: a weight other than 0 and 2 is served (hx_map2alm, hx_alm2map)
 // hx_analysis.hip
-int build_tasks(hx_plan *pl, int spin);
+int one_set_task_blocks(int spin);   // ring blocks per task of k_legendre_duo and k_synth_duo: one ring set per wave
+int flop_task_blocks(int spin);      // ring blocks per task of the set the flop accounting and hx_ring_modes count with
 int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 *d_alms, const double *d_rw,
                    const double *d_pw, const double *d_fl, int add);
 // A spin weight that runs through the run-time-spin sweep of the vector unit, one (Q, U) field at a time: any but 0 and 2, and
@@ -443,6 +447,8 @@ struct StreamSweep {
     double2 *d_alms = nullptr;
     std::vector<int> rp_edge;   // slab k = ring pairs [rp_edge[k], rp_edge[k + 1]): whole 32-ring-pair blocks, about equal numbers of pixels
     DevBuf d_of_m;              // [nslab][lmax + 1]: the ring groups of order m that are complete with slab k
+    hx_plan::SpinData *sd = nullptr;  // tables and tasks (one ring set per wave) the sweep runs with
+    hx_plan::TaskSet *ts = nullptr;
 };
 bool analysis_can_stream(hx_plan *pl, int spin, int nb);
 int analysis_stream_plan(hx_plan *pl, int spin, int nb, int nslab, StreamSweep &s);   // slab edges, task tables, scratch (grown, never shrunk): before anything of the call is queued
@@ -450,19 +456,18 @@ int analysis_stream_start(StreamSweep &s);  // zeroes the accumulation rows (que
 int analysis_stream_slab(StreamSweep &s, int k);
 int analysis_stream_end(StreamSweep &s);
 // hx_legendre_valu.hip: one map (spin 0) / one field (spin 2) per sweep on the FP64 vector unit
-int launch_valu_chunk(hx_plan *pl, int spin, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic = false);
+int launch_valu_chunk(hx_plan *pl, int spin, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, int m0, int m1, int c0, const double *d_rw, bool generic = false);
 int valu_task_blocks(int spin);      // 32-ring-pair blocks per task
 int valu_partial_cols(int spin);     // doubles per row of the partial buffer
 int valu_operand_doubles(int spin);  // doubles per (m, ring pair) of the operand array
 int valu_exec_flops(unsigned long long *v, bool reset);
-int valu_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **ts, int blocks = 0, bool generic = false);  // (hx_analysis.hip) task set of the vector-unit kernels (blocks: 32-ring-pair blocks per task, 0 = valu_task_blocks), built on first use
 int synth_valu_max_units(int spin);                // maps (spin 0) / fields (spin 2) per sweep of the synthesis kernel: 1, 2, .. a power of two
 int synth_valu_task_blocks(int spin, int units);   // ring blocks per task of that sweep
-int launch_synth_valu(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic = false);  // generic: the run-time-spin sweep (one field, ts of valu_tasks(.., true))
+int launch_synth_valu(hx_plan *pl, int spin, int units, const hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_Fv, bool generic = false);  // generic: the run-time-spin sweep (one field, ts of its family)
 // hx_synth_duo.hip: up to 20 maps / 10 fields per sweep on the matrix unit; Fv[m][rp][synth_duo_rowlen] in the lane order of that kernel
 int synth_duo_max_units(int spin);
 int synth_duo_rowlen(int spin, int units);
 size_t synth_duo_table_bytes(hx_plan *pl, int spin, int units);
-int launch_synth_duo(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_tab, double *d_Fv);
-int synth_duo_tasks(hx_plan *pl, int spin, hx_plan::TaskSet **ts);  // (hx_analysis.hip) tasks of 8 (spin 0) / 4 (spin 2) ring blocks: the ring groups of k_legendre_duo  // alm -> Fv[m][rp][4 per component]  // FP64 vector flops executed by the vector-unit kernels since the last reset
+int synth_duo_min_units(int spin);   // the smallest batch worth a sweep of the matrix kernel
+int launch_synth_duo(hx_plan *pl, int spin, int units, hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_tab, double *d_Fv);  // ts: tasks of one_set_task_blocks(spin)
 }  // namespace hx

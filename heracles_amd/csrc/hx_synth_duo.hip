@@ -449,6 +449,7 @@ static SynShape syn_shape(int spin, int units)
     return best;
 }
 int synth_duo_max_units(int spin) { return spin ? 10 : 20; }
+int synth_duo_min_units(int spin) { return spin ? 3 : 5; }
 int synth_duo_rowlen(int spin, int units) { return (spin ? 8 : 4) * units; }
 
 template <int SPIN, int NG, int NBX>
@@ -469,13 +470,13 @@ size_t synth_duo_table_bytes(hx_plan *pl, int spin, int units)
     return (size_t)nblk * (sh.ng * 256 + sh.nbx * 64) * sizeof(double);
 }
 
-int launch_synth_duo(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_tab, double *d_Fv)
+int launch_synth_duo(hx_plan *pl, int spin, int units, hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double2 *d_alm, double *d_tab, double *d_Fv)
 {
     if (units < 1 || units > synth_duo_max_units(spin)) return fail(HX_ERR_ARG, "launch_synth_duo: %d units of spin %d", units, spin);
     hipStream_t st = rt().stream;
     const SynShape sh = syn_shape(spin, units);
     // first table block of every m (the same for every shape: blocks are counted, not bytes)
-    DevBuf &boff = spin ? pl->syn_boff2 : pl->syn_boff0;
+    DevBuf &boff = sd.syn_boff;
     if (!boff.p) {
         std::vector<long long> h(pl->lmax + 2, 0);
         for (int m = 0; m <= pl->lmax; ++m) {
@@ -484,10 +485,10 @@ int launch_synth_duo(hx_plan *pl, int spin, int units, hx_plan::TaskSet &ts, con
         }
         HX_TRY(upload(boff, h));
     }
-    const double2 *cn = spin == 0 ? pl->cn0.as<double2>() : pl->cn2.as<double2>();
-    const double *al = spin == 0 ? pl->al0.as<double>() : pl->al2.as<double>();
+    const double2 *cn = sd.cn.as<double2>();
+    const double *al = sd.al.as<double>();
     const int rowlen = synth_duo_rowlen(spin, units);
-    // (rows of pruned rings are not written: k_synth_spectrum_v is told where they begin, hx_plan::syn_mlim*)
+    // (rows of pruned rings are not written: k_synth_spectrum_v is told where they begin, hx_plan::SpinData::syn_mlim)
     {
         ProfScope ps("synth_table");
         const dim3 grid(pl->lmax + 1, 8);

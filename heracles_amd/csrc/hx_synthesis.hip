@@ -136,9 +136,11 @@ static int synthesis_batch_valu(hx_plan *pl, int spin, int nb, const double2 *d_
         int units = umax;
         while (units * cpu > nb - c0) units >>= 1;
         const int nc = units * cpu;
+        hx_plan::SpinData *sd = nullptr;
         hx_plan::TaskSet *ts = nullptr;
-        HX_TRY(valu_tasks(pl, spin, &ts, synth_valu_task_blocks(spin, units), generic));
-        HX_TRY(launch_synth_valu(pl, spin, units, *ts, d_alms + (size_t)c0 * pl->nlm, fsyn, generic));
+        HX_TRY(spin_data(pl, spin, generic, &sd));
+        HX_TRY(task_set(pl, spin, generic, synth_valu_task_blocks(spin, units), &ts));
+        HX_TRY(launch_synth_valu(pl, spin, units, *sd, *ts, d_alms + (size_t)c0 * pl->nlm, fsyn, generic));
         ProfScope ps("ring_fft");
         hipLaunchKernelGGL(k_synth_spectrum_v, dim3((pl->nrp + 3) / 4), dim3(256), 0, st, P, fsyn, nc, pl->lmax, zc, (const int *)nullptr, pl->nrp);
         // inverse sub-DFTs whose read-out writes the pixels (or the residual ref - synthesised of a Jacobi iteration) itself
@@ -171,10 +173,15 @@ int hx::synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, do
     // modes (Fv) and ring spectra (conj Z) live in the analysis' operand buffer F, which is idle during a synthesis: a Jacobi iteration
     // of ten fields needs no HBM beyond what its analysis passes hold (F 64 GB >= 32 + 32).
     const int nunits_all = nb / cpu;
-    if (nunits_all >= (spin ? 3 : 5)) {
+    const int umin = synth_duo_min_units(spin);
+    if (nunits_all >= umin) {
         const int umax = synth_duo_max_units(spin);
+        hx_plan::SpinData *sd = nullptr;
         hx_plan::TaskSet *ts = nullptr;
-        HX_TRY(synth_duo_tasks(pl, spin, &ts));
+        const int *ml = nullptr;  // rows of Fv beyond ml[rp] are neither written nor read
+        HX_TRY(spin_data(pl, spin, false, &sd));
+        HX_TRY(task_set(pl, spin, false, one_set_task_blocks(spin), &ts));
+        HX_TRY(synth_mlim(pl, spin, &ml));
         // what a sweep of `units` holds: ring modes + ring spectra (in F), the B-operand table
         auto sweep_bytes = [&](int units) {
             const double nc = (double)units * cpu;
@@ -188,12 +195,12 @@ int hx::synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, do
         for (int u0 = 0; u0 < nunits_all;) {
             int units = std::min(umax, nunits_all - u0);
             // (a remainder of one or two units would run a whole sweep of the matrix kernel for 4-8 columns: split the tail evenly instead)
-            if (nunits_all - u0 > umax && nunits_all - u0 < umax + (spin ? 3 : 5)) units = (nunits_all - u0 + 1) / 2;
+            if (nunits_all - u0 > umax && nunits_all - u0 < umax + umin) units = (nunits_all - u0 + 1) / 2;
             // a sweep that does not fit the free HBM (nside 8192: 213 + 129 GB for ten fields) is cut down; below the matrix kernel's
             // smallest useful batch the rest goes to the vector-unit kernel's sweeps of four maps / two fields
             while (units > 1 && sweep_bytes(units) > avail) --units;
-            if (units < (spin ? 3 : 5) && sweep_bytes(units) > avail) units = 0;
-            if (units < (spin ? 3 : 5) && (units == 0 || nunits_all - u0 >= (spin ? 3 : 5))) {
+            if (units < umin && sweep_bytes(units) > avail) units = 0;
+            if (units < umin && (units == 0 || nunits_all - u0 >= umin)) {
                 HX_TRY(synthesis_batch_valu(pl, spin, (nunits_all - u0) * cpu, d_alms + (size_t)u0 * cpu * pl->nlm, d_maps + (size_t)u0 * cpu * pl->npix,
                                             d_ref ? d_ref + (size_t)u0 * cpu * pl->npix : nullptr));
                 break;
@@ -206,11 +213,10 @@ int hx::synthesis_batch(hx_plan *pl, int spin, int nb, const double2 *d_alms, do
             HX_TRY(pl->syn_tab.alloc(synth_duo_table_bytes(pl, spin, units)));
             double *fv = pl->F.as<double>();
             double2 *zc = reinterpret_cast<double2 *>(reinterpret_cast<char *>(pl->F.p) + fv_pad);
-            HX_TRY(launch_synth_duo(pl, spin, units, *ts, d_alms + (size_t)u0 * cpu * pl->nlm, pl->syn_tab.as<double>(), fv));
+            HX_TRY(launch_synth_duo(pl, spin, units, *sd, *ts, d_alms + (size_t)u0 * cpu * pl->nlm, pl->syn_tab.as<double>(), fv));
             ProfScope ps("ring_fft");
             {
                 // ring pairs whose rings hold every order in a bin of its own go through the transposing pass, the polar ones through the gather
-                const int *ml = (spin ? pl->syn_mlim2 : pl->syn_mlim0).as<int>();
                 int rp_t = pl->nrp;
                 while (rp_t > 0 && 4 * pl->h_nsub[rp_t - 1] >= 2 * pl->lmax + 2) --rp_t;
                 if (rp_t > 0)
