@@ -28,7 +28,7 @@ SYMBOLS = (
     "hx_profile_enable", "hx_profile_reset", "hx_profile_get", "hx_plan_create", "hx_set_max_lds_fft",
     "hx_plan_destroy", "hx_plan_scratch_bytes", "hx_plan_release_scratch", "hx_set_scratch_budget", "hx_plan_last_chunks", "hx_plan_mfma_flops", "hx_plan_executed_flops", "hx_executed_flops", "hx_measure_peaks", "hx_measured_mfma_clock", "hx_map2alm", "hx_map2alm_multi", "hx_map2alm_list", "hx_alm2map", "hx_copy",
     "hx_alm2cl_pairs", "hx_alm2cl_pairs_range", "hx_gauss_legendre", "hx_gauss_legendre_dd", "hx_wigner_d_table", "hx_mixmat",
-    "hx_mixmat_eb", "hx_mixmat_eb_spin", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_apply_spin", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_mixctx_apply_binned_spin", "hx_cl2corr", "hx_corr2cl", "hx_cl2corr_cols", "hx_corr2cl_cols", "hx_xi_ratio", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64", "hx_fits_unpack_columns",
+    "hx_mixmat_eb", "hx_mixmat_eb_spin", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_apply_spin", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_mixctx_apply_binned_spin", "hx_cl2corr", "hx_corr2cl", "hx_cl2corr_cols", "hx_corr2cl_cols", "hx_cl2corr_cols_spin", "hx_corr2cl_cols_spin", "hx_xi_ratio", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64", "hx_fits_unpack_columns",
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
     "hx_pixel_weights_size", "hx_pixel_weights_expand",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
@@ -117,6 +117,8 @@ def load():
         L.hx_corr2cl.argtypes = [i, i, dp, dp]
         L.hx_cl2corr_cols.argtypes = [i, i, i, vp, dp, dp]
         L.hx_corr2cl_cols.argtypes = [i, i, i, vp, dp, dp]
+        L.hx_cl2corr_cols_spin.argtypes = [i, i, i, vp, dp, dp]
+        L.hx_corr2cl_cols_spin.argtypes = [i, i, i, vp, dp, dp]
         L.hx_xi_ratio.argtypes = [i, i, dp, dp, vp, dp, vp, vp, C.c_double, C.c_double, dp]
         L.hx_ang2pix_ring.argtypes = [i, C.c_int64, dp, dp, dp]
         L.hx_map_values.argtypes = [i, C.c_int64, dp, dp, i, dp, dp, i]
@@ -253,7 +255,8 @@ def release_caches():
     """Hand back the HBM the library keeps between calls outside plans and contexts: the cache of ``mixmat`` / ``mixmat_eb`` (tables of
     the last sizes + host-staging buffer, ~3 GB at L = 6144), the buffers of ``alm2cl_pairs`` (<= 512 MB) and the nodes, weights and
     Wigner tables ``cl2corr`` / ``corr2cl`` / ``naturalspice`` keep for their last lmax (1.2 GB at lmax 6144; the column transforms of
-    ``naturalspice_batch`` read the same tables and keep nothing of their own): hx_release_caches."""
+    ``naturalspice_batch`` read the same tables and keep nothing of their own; with ``exact_spin`` up to ``HX_XI_TABLES`` pair tables of
+    0.31 GB each at lmax 6144 lie beside them): hx_release_caches."""
     check(load().hx_release_caches())
 
 

@@ -125,6 +125,17 @@ int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  
 // Gauss-Legendre nodes/weights into device arrays (hx_mixmat.hip)
 int launch_gauss_legendre(int n, double *d_x, double *d_w, double *d_xlo = nullptr);  // d_xlo: node k = x[k] + xlo[k] (see k_gauss_legendre)
 
+// Wigner-d tables of any pair by k_wigner_table_dd (hx_mixmat.hip), for the pair tables of the Cl <-> xi columns:
+//   wigner_pair_normalise: (a, b) brought to A >= |B|, A >= 0 by d_{ab} = (-1)^{a-b} d_{ba} = d_{-b,-a} (the pair under which the
+//     mixing-matrix context keeps its tables); returns the sign s with d_{ab} = s d_{AB};
+//   wigner_table_build: out[l * sl + k * sk] = d^l_{ab}(x_k + xlo_k), l = 0 .. lmax (0 below max(|a|, |b|)), device pointers, on the
+//     library stream; complete on return.
+double wigner_pair_normalise(int a, int b, int *A, int *B);
+int wigner_table_build(int lmax, int a, int b, int n, const double *d_x, const double *d_xlo, double *d_out, long long sl, long long sk);
+// hx_transforms.hip: the cached table [lmax + 1][kpad] of the normalised pair (A, B) at the lmax + 1 Gauss-Legendre nodes and their
+// weights w, for hx_xi_cols.hip (built on first use; see PairCache for how long the pointers hold)
+int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **w, int *kpad);
+
 // The two halves of hx_pointsht_adjoint (hx_nufft.hip), for callers that keep grids resident (hx_catalm, hx_mapper.hip).
 // Half one: pointsht_order picks the spreading path for n points (tiles from 300000 points, HX_NUFFT_TILES forces it) and sorts them
 // by tile when that path is taken -- once for every component spread from these points; pointsht_spread_one ADDS one component

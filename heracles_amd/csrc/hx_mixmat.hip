@@ -731,6 +731,20 @@ static int upload_vec(DevBuf &b, const std::vector<T> &v)
     return HX_OK;
 }
 
+// The two below serve the pair tables of the Cl <-> xi columns (hx_transforms.hip: xi_pair_table_view), declared in hx_common.h: the
+// normalisation under which pairs share a table, and one table by the kernel above in the caller's layout.
+double wigner_pair_normalise(int a, int b, int *A, int *B) { return wigner_normal_pair(a, b, *A, *B); }
+int wigner_table_build(int lmax, int a, int b, int n, const double *d_x, const double *d_xlo, double *d_out, long long sl, long long sk)
+{
+    std::vector<WigCoefDD> coef;
+    wigner_coefs_dd(lmax, a, b, coef);
+    DevBuf d_coef;
+    HX_TRY(upload_vec(d_coef, coef));
+    HX_TRY(launch_wigner_table(lmax, a, b, n, d_x, d_xlo, d_coef.as<WigCoefDD>(), d_out, sl, sk));
+    HX_HIP(hipStreamSynchronize(rt().stream));  // d_coef dies with this scope
+    return HX_OK;
+}
+
 struct GLCache {
     int n = 0;
     DevBuf x, w, xlo;  // node k = x[k] + xlo[k]

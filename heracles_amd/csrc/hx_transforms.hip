@@ -8,6 +8,9 @@
 // coalesced stores), then both directions are dense contractions over l or over k.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <memory>
+#include <vector>
 
 #include "hx_common.h"
 
@@ -159,7 +162,91 @@ int corr_tables_view(int lmax, const double **T, const double **w, int *kpad)
     return HX_OK;
 }
 
-// hx_release_caches: the nodes, weights and the four tables of the last lmax (4 (lmax + 1) kpad doubles: 1.2 GB at lmax 6144)
+// Tables of single pairs for the columns of any spin weight (hx_cl2corr_cols_spin / hx_corr2cl_cols_spin): T_{AB}[l][k] = d^l_{AB}(x_k),
+// [lmax + 1][kpad] doubles, kpad = ceil64(lmax + 1), by the double-double recursion of the mixing-matrix tables (k_wigner_table_dd
+// through wigner_table_build, written straight into this layout) at the Gauss-Legendre nodes with their low parts; the weights are
+// the bits the family path uses (k_gauss_legendre writes the same x, w with or without xlo).  Keyed by lmax and the NORMALISED pair
+// (A >= |B|, wigner_pair_normalise): (a, b), (b, a), (-b, -a) and (-a, -b) share one table and the caller applies the sign that
+// normalisation leaves.  At most max_tabs tables are kept (env HX_XI_TABLES at first use, default 8, at least 2: a four-column key
+// reads two), the one used longest ago is dropped for a new one; another lmax drops them all.
+struct PairTable {
+    int a = 0, b = 0;
+    DevBuf T;
+    unsigned long long used = 0;
+};
+struct PairCache {
+    int lmax = -1, n = 0, kpad = 0, max_tabs = 0;
+    DevBuf x, xlo, w;
+    std::vector<std::unique_ptr<PairTable>> tabs;
+    unsigned long long tick = 0;
+};
+
+static PairCache &pair_cache()
+{
+    static PairCache c;
+    return c;
+}
+
+static void pair_cache_clear(PairCache &c)
+{
+    c.tabs.clear();
+    c.x.release();
+    c.xlo.release();
+    c.w.release();
+    c.lmax = -1;
+    c.n = c.kpad = 0;
+}
+
+// *T holds until the next call of this function with a pair that is not cached, *w until the next call with another lmax (or
+// corr_cache_drop()).  Before a table is dropped the library stream is synchronised: launches of the call in hand that read it are done
+// by then, so a caller may walk more pairs than the cache holds, one launch after the other.
+int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **w, int *kpad)
+{
+    PairCache &c = pair_cache();
+    hipStream_t st = rt().stream;
+    if (!c.max_tabs) {
+        c.max_tabs = 8;
+        if (const char *e = getenv("HX_XI_TABLES")) c.max_tabs = std::max(2, atoi(e));
+    }
+    if (c.lmax != lmax || !c.w.p) {
+        HX_HIP(hipStreamSynchronize(st));
+        pair_cache_clear(c);
+        const int n = lmax + 1;
+        HX_TRY(c.x.alloc(sizeof(double) * n));
+        HX_TRY(c.xlo.alloc(sizeof(double) * n));
+        HX_TRY(c.w.alloc(sizeof(double) * n));
+        HX_TRY(launch_gauss_legendre(n, c.x.as<double>(), c.w.as<double>(), c.xlo.as<double>()));
+        c.lmax = lmax; c.n = n; c.kpad = (n + 63) / 64 * 64;
+    }
+    *w = c.w.as<double>();
+    *kpad = c.kpad;
+    for (auto &t : c.tabs)
+        if (t->a == A && t->b == B) {
+            t->used = ++c.tick;
+            *T = t->T.as<double>();
+            return HX_OK;
+        }
+    if ((int)c.tabs.size() >= c.max_tabs) {
+        size_t old = 0;
+        for (size_t i = 1; i < c.tabs.size(); ++i)
+            if (c.tabs[i]->used < c.tabs[old]->used) old = i;
+        HX_HIP(hipStreamSynchronize(st));  // (a launch may still be reading it)
+        c.tabs.erase(c.tabs.begin() + old);
+    }
+    std::unique_ptr<PairTable> t(new PairTable);
+    t->a = A; t->b = B;
+    const size_t bytes = sizeof(double) * (size_t)(lmax + 1) * c.kpad;
+    HX_TRY(t->T.alloc(bytes));
+    HX_HIP(hipMemsetAsync(t->T.p, 0, bytes, st));
+    HX_TRY(wigner_table_build(lmax, A, B, c.n, c.x.as<double>(), c.xlo.as<double>(), t->T.as<double>(), (long long)c.kpad, 1LL));
+    t->used = ++c.tick;
+    *T = t->T.as<double>();
+    c.tabs.push_back(std::move(t));
+    return HX_OK;
+}
+
+// hx_release_caches: the nodes, weights and the four tables of the last lmax (4 (lmax + 1) kpad doubles: 1.2 GB at lmax 6144), and the
+// pair tables beside them ((lmax + 1) kpad doubles each: 0.31 GB at lmax 6144, HX_XI_TABLES of them at most)
 void corr_cache_drop()
 {
     CorrCache &c = corr_cache();
@@ -168,6 +255,7 @@ void corr_cache_drop()
     c.T.release();
     c.lmax = -1;
     c.n = c.kpad = 0;
+    pair_cache_clear(pair_cache());
 }
 
 }  // namespace hx

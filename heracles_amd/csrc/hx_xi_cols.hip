@@ -18,6 +18,11 @@
 //
 // Nothing is kept between calls but the tables hx_cl2corr already caches (corr_tables_view: one owner, hx_release_caches frees
 // them); index lists and factors are temporaries of the call.
+//
+// Columns of any spin weight (hx_cl2corr_cols_spin / hx_corr2cl_cols_spin, xi_columns_spin below) are tied to a pair (a, b) instead of
+// a family: the same kernels against T_{ab}[l][k] = d^l_{ab}(x_k) with l0 = max(|a|, |b|), one launch per distinct pair, tables from
+// the pair cache beside the family tables (xi_pair_table_view in hx_transforms.hip: one owner, bounded, freed by hx_release_caches).
+#include <algorithm>
 #include <vector>
 
 #include "hx_common.h"
@@ -259,10 +264,109 @@ int xi_columns(bool fwd, int lmax, int nl, int ncol, const int *family, const do
     return HX_OK;
 }
 
+__global__ void k_xi_negate(int n, const double *__restrict__ src, double *__restrict__ dst)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = -src[i];
+}
+
+// Columns tied to a PAIR (a, b) instead of a family: column c runs on T_{ab}[l][k] = d^l_{ab}(x_k) with l0 = max(|a|, |b|), the same two
+// kernels, one launch per distinct pair.  Pairs share the table of their normalised pair (xi_pair_table_view); where the
+// normalisation leaves a minus sign (d_{12} = -d_{21}) the launch gets the negated factors (forward) or weights (back): every product
+// of the contraction changes its sign and nothing else, so the result is the bits of the shared table's, negated.  The determinism
+// statement at the top holds as it stands: a column's accumulator sees its pair's table, factors and weights, whatever else is in the
+// batch, and the order of the launches does not enter.
+int xi_columns_spin(bool fwd, int lmax, int nl, int ncol, const int *pairs, const double *src, double *dst)
+{
+    const char *name = fwd ? "hx_cl2corr_cols_spin" : "hx_corr2cl_cols_spin";
+    HX_TRY(ensure_ready());
+    if (lmax < 0 || nl < 1 || nl > lmax + 1 || ncol < 1 || !pairs || !src || !dst) return fail(HX_ERR_ARG, "%s: bad argument", name);
+    // columns by (A, B, sign): the launches of pairs that share a table follow each other
+    struct Group {
+        int A, B, neg, l0;
+        std::vector<int> cols;
+    };
+    std::vector<Group> groups;
+    for (int c = 0; c < ncol; ++c) {
+        const int a = pairs[2 * c], b = pairs[2 * c + 1];
+        if (std::max(abs(a), abs(b)) > HX_MAX_MIX_SPIN)
+            return fail(HX_ERR_UNSUPPORTED, "%s: (a,b)=(%d,%d) beyond the supported max(|a|,|b|) <= %d", name, a, b, HX_MAX_MIX_SPIN);
+        int A, B;
+        const int neg = wigner_pair_normalise(a, b, &A, &B) < 0.0;
+        size_t g = 0;
+        while (g < groups.size() && !(groups[g].A == A && groups[g].B == B && groups[g].neg == neg)) ++g;
+        if (g == groups.size()) groups.push_back(Group{A, B, neg, A, {}});
+        groups[g].cols.push_back(c);
+    }
+    std::stable_sort(groups.begin(), groups.end(), [](const Group &x, const Group &y) { return x.A != y.A ? x.A < y.A : x.B < y.B; });
+    std::vector<int> idx;
+    idx.reserve(ncol);
+    bool any_neg = false;
+    for (const Group &g : groups) {
+        idx.insert(idx.end(), g.cols.begin(), g.cols.end());
+        any_neg = any_neg || g.neg;
+    }
+    const int n = lmax + 1;
+    hipStream_t st = rt().stream;
+    InView vi;
+    OutView vo;
+    HX_TRY(vi.bind(src, sizeof(double) * (size_t)ncol * (fwd ? nl : n)));
+    HX_TRY(vo.bind(dst, sizeof(double) * (size_t)ncol * (fwd ? n : nl)));
+    DevBuf d_idx, d_f;  // d_f: factors | negated factors (forward), negated weights (back)
+    HX_TRY(d_idx.alloc(sizeof(int) * (size_t)ncol));
+    HX_HIP(hipMemcpyAsync(d_idx.p, idx.data(), sizeof(int) * (size_t)ncol, hipMemcpyHostToDevice, st));
+    if (fwd) {
+        HX_TRY(d_f.alloc(sizeof(double) * (size_t)2 * nl));
+        hipLaunchKernelGGL(k_xi_factors, dim3((nl + 255) / 256), dim3(256), 0, st, nl, d_f.as<double>());
+        if (any_neg) hipLaunchKernelGGL(k_xi_negate, dim3((nl + 255) / 256), dim3(256), 0, st, nl, d_f.as<double>(), d_f.as<double>() + nl);
+    } else if (any_neg) {
+        HX_TRY(d_f.alloc(sizeof(double) * (size_t)n));
+    }
+    bool have_wneg = false;
+    {
+        ProfScope ps(fwd ? "xi_cols_fwd" : "xi_cols_back");
+        int off = 0;
+        for (const Group &g : groups) {
+            const int nc = (int)g.cols.size();
+            const double *T, *w;
+            int kpad;
+            HX_TRY(xi_pair_table_view(lmax, g.A, g.B, &T, &w, &kpad));  // (the weights stay where they are for the whole call: one lmax)
+            const dim3 grid(((fwd ? n : nl) + XT - 1) / XT, (nc + XT - 1) / XT);
+            if (fwd) {
+                hipLaunchKernelGGL(k_xi_fwd, grid, dim3(256), 0, st, nl, n, kpad, g.l0, T, d_f.as<double>() + (g.neg ? nl : 0), d_idx.as<int>() + off, nc,
+                                   vi.as<double>(), vo.as<double>());
+            } else {
+                if (g.neg && !have_wneg) {
+                    hipLaunchKernelGGL(k_xi_negate, dim3((n + 255) / 256), dim3(256), 0, st, n, w, d_f.as<double>());
+                    have_wneg = true;
+                }
+                hipLaunchKernelGGL(k_xi_back, grid, dim3(256), 0, st, nl, n, kpad, g.l0, T, g.neg ? d_f.as<const double>() : w, d_idx.as<int>() + off, nc,
+                                   vi.as<double>(), vo.as<double>());
+            }
+            off += nc;
+        }
+    }
+    HX_HIP(hipGetLastError());
+    HX_TRY(vo.finish());
+    HX_HIP(hipStreamSynchronize(st));  // the index list, the factors and the negated weights die with this scope
+    return HX_OK;
+}
+
 }  // namespace
 }  // namespace hx
 
 using namespace hx;
+
+extern "C" int hx_cl2corr_cols_spin(int lmax, int nl, int ncol, const int *pairs, const double *a, double *xi)
+{
+    return xi_columns_spin(true, lmax, nl, ncol, pairs, a, xi);
+}
+
+extern "C" int hx_corr2cl_cols_spin(int lmax, int nl, int ncol, const int *pairs, const double *xi, double *b)
+{
+    return xi_columns_spin(false, lmax, nl, ncol, pairs, xi, b);
+}
+
 
 extern "C" int hx_cl2corr_cols(int lmax, int nl, int ncol, const int *family, const double *a, double *xi)
 {

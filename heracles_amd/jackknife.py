@@ -215,10 +215,13 @@ def correct_footprint_naturalspice(cls, cls_mm, mls0, fields, unmixed=False):
     return _pad(corr2cl(wcls), lmax)
 
 
-def correct_footprint_naturalspice_batch(cls_by_sample, cls_mm_by_sample, mls0, fields, unmixed=False, max_columns=None, ops=None):
+def correct_footprint_naturalspice_batch(cls_by_sample, cls_mm_by_sample, mls0, fields, unmixed=False, max_columns=None, ops=None,
+                                         exact_spin=False):
     """``{id: correct_footprint_naturalspice(cls_by_sample[id], cls_mm_by_sample[id], mls0, fields, unmixed)}`` with all samples in
     one batch of columns on the matrix unit (unmixing.run_spice_plan): the data columns of every sample divide by the damped
-    alpha = xi(that sample's jackknife mask) [/ xi(full mask), shared], and come back cut at the data's band limit."""
+    alpha = xi(that sample's jackknife mask) [/ xi(full mask), shared], and come back cut at the data's band limit.  ``exact_spin``:
+    keys with a spin outside {0, 2} run on the Wigner functions of their own spins (``unmixing.spice_plan``); the per-sample function
+    above and ``jackknife_cls`` do not take it yet."""
     from .unmixing import _band_limit, _check_samples, _dress, _pack_spectra, run_spice_plan, spice_plan
 
     ids, first, n_data = _check_samples(cls_by_sample)
@@ -235,7 +238,7 @@ def correct_footprint_naturalspice_batch(cls_by_sample, cls_mm_by_sample, mls0, 
             raise ValueError("all mask samples must have the same keys, spins and the band limit of mls0")
     if any(k not in mls0 or tuple(mls0[k].spin) != sp for k, sp in m_spins.items()):
         raise KeyError("mls0 lacks a key of the jackknife mask spectra")
-    plan = spice_plan({k: tuple(r.spin) for k, r in first.items()}, m_spins, fields)
+    plan = spice_plan({k: tuple(r.spin) for k, r in first.items()}, m_spins, fields, exact_spin=exact_spin)
     data = np.stack([_pack_spectra(cls_by_sample[i], n_data) for i in ids])
     num = np.stack([_pack_spectra(cls_mm_by_sample[i], n_mask) for i in ids])
     den = None if unmixed else _pack_spectra({k: mls0[k] for k in m_spins}, n_mask)

@@ -113,11 +113,64 @@ def _ell_len(res):
     return len(ell)
 
 
-def cl2corr(cls):
-    """Dict of Result spectra -> dict of correlation functions (transforms.py:207-283)."""
+def _exact_key(spin):
+    """Whether a key of these spins leaves the reference's "like spin 2" rule under ``exact_spin``: any spin outside {0, 2}."""
+    return any(abs(int(s)) not in (0, 2) for s in spin)
+
+
+def spin_pairs(spin):
+    """The (a, b) of the columns of a spectrum of spins (s1, s2), one row per column: (0,0) on T_00; one spin zero: two columns on
+    T_{s,0}; both non-zero: two on T_{s1,s2}, two on T_{s1,-s2}, in the key's own order of the spins."""
+    s1, s2 = (int(s) for s in spin)
+    if s1 != 0 and s2 != 0:
+        return [(s1, s2), (s1, s2), (s1, -s2), (s1, -s2)]
+    if s1 != 0 or s2 != 0:
+        return [(s1 or s2, 0)] * 2
+    return [(0, 0)]
+
+
+def _exact_columns(fn, items, pack):
+    """Columns of the keys of ``items`` ({key: Result}) through the pair path, one call per band limit: {key: (ncols, length)}."""
+    out = {}
+    for lm in sorted({_ell_len(r) - 1 for r in items.values()}):
+        keys = [k for k, r in items.items() if _ell_len(r) - 1 == lm]
+        cols = [pack(np.asarray(items[k].array, dtype=np.float64), items[k].spin) for k in keys]
+        pairs = np.concatenate([np.asarray(spin_pairs(items[k].spin), dtype=np.int32) for k in keys])
+        res = fn(np.concatenate(cols), pairs, lm)
+        at = 0
+        for k, c in zip(keys, cols):
+            out[k] = res[at : at + len(c)]
+            at += len(c)
+    return out
+
+
+def _pack_fwd(a, spin):
+    s1, s2 = spin
+    if s1 != 0 and s2 != 0:
+        return np.stack([a[0, 0] + a[1, 1], a[1, 0] - a[0, 1], -a[0, 1] - a[1, 0], a[0, 0] - a[1, 1]])
+    return np.stack([a[0] + a[1], a[0] - a[1]])
+
+
+def _pack_back(a, spin):
+    s1, s2 = spin
+    if s1 != 0 and s2 != 0:
+        return np.stack([a[0, 0], a[0, 1], a[1, 0], a[1, 1]])
+    return np.stack([a[0], a[1]])
+
+
+def cl2corr(cls, exact_spin=False):
+    """Dict of Result spectra -> dict of correlation functions (transforms.py:207-283).
+
+    The reference transforms every non-zero spin "like spin 2".  With ``exact_spin`` a key with a spin outside {0, 2} runs on the
+    Wigner functions of its own spins instead (``cl2corr_columns`` with pairs: d^l_{s,0}, d^l_{s1,s2}, d^l_{s1,-s2}), placed as the
+    spin-2 cases are; keys of spins {0, 2} go as without it, bit for bit."""
     L = _lib.load()
+    exact = {key: cl for key, cl in cls.items() if exact_spin and _exact_key(cl.spin)}
+    xi_exact = _exact_columns(cl2corr_columns, exact, _pack_fwd) if exact else {}
     work, plan = [], []
     for key, cl in cls.items():
+        if key in exact:
+            continue
         s1, s2 = cl.spin
         lmax = _ell_len(cl) - 1
         a = np.asarray(cl.array)
@@ -136,12 +189,20 @@ def cl2corr(cls):
         res = _batch(L.hx_cl2corr, [work[i][1] for i in ids], lm)
         for i, r in zip(ids, res):
             outs[i] = r
+    plan = {p[0]: p for p in plan}
     wds = {}
-    for key, lmax, start, n in plan:
-        cl = cls[key]
+    for key, cl in cls.items():
         s1, s2 = cl.spin
-        xvals, _ = gauss_legendre(lmax + 1)
         a = np.asarray(cl.array)
+        if key in exact:
+            lmax = _ell_len(cl) - 1
+            xvals, _ = gauss_legendre(lmax + 1)
+            wd = np.zeros_like(a)
+            wd[...] = np.asarray(xi_exact[key]).reshape(a.shape)  # (column j is flat position j, as in the spin-2 placement below)
+            wds[key] = replace(cl, ell=xvals, array=np.array(list(wd), dtype=a.dtype))
+            continue
+        _, lmax, start, n = plan[key]
+        xvals, _ = gauss_legendre(lmax + 1)
         wd = np.zeros_like(a)
         if s1 != 0 and s2 != 0:
             r, i = outs[start].T, outs[start + 1].T
@@ -155,11 +216,15 @@ def cl2corr(cls):
     return wds
 
 
-def corr2cl(wds):
-    """Dict of correlation functions -> dict of spectra (transforms.py:286-363)."""
+def corr2cl(wds, exact_spin=False):
+    """Dict of correlation functions -> dict of spectra (transforms.py:286-363); ``exact_spin`` as in ``cl2corr``."""
     L = _lib.load()
+    exact = {key: wd for key, wd in wds.items() if exact_spin and _exact_key(wd.spin)}
+    b_exact = _exact_columns(corr2cl_columns, exact, _pack_back) if exact else {}
     work, plan = [], []
     for key, wd in wds.items():
+        if key in exact:
+            continue
         s1, s2 = wd.spin
         lmax = _ell_len(wd) - 1
         a = np.asarray(wd.array)
@@ -178,11 +243,22 @@ def corr2cl(wds):
         res = _batch(L.hx_corr2cl, [work[i][1] for i in ids], lm)
         for i, r in zip(ids, res):
             outs[i] = r
+    plan = {p[0]: p for p in plan}
     cls = {}
-    for key, lmax, start, n in plan:
-        wd = wds[key]
+    for key, wd in wds.items():
         s1, s2 = wd.spin
         a = np.asarray(wd.array)
+        if key in exact:
+            lmax = _ell_len(wd) - 1
+            b = b_exact[key]
+            cl = np.zeros_like(a)
+            if s1 != 0 and s2 != 0:
+                cl[0, 0], cl[1, 1], cl[0, 1], cl[1, 0] = (b[0] + b[3]) / 2, (b[0] - b[3]) / 2, -(b[1] + b[2]) / 2, (b[1] - b[2]) / 2
+            else:
+                cl[0], cl[1] = (b[0] + b[1]) / 2, (b[0] - b[1]) / 2
+            cls[key] = replace(wd, ell=np.arange(lmax + 1), array=np.array(list(cl), dtype=a.dtype))
+            continue
+        _, lmax, start, n = plan[key]
         cl = np.zeros_like(a)
         if s1 != 0 and s2 != 0:
             r, i = outs[start].T, outs[start + 1].T
@@ -231,32 +307,49 @@ def _index(ix, ncol, what):
     return ix
 
 
+def _families(families, ncol):
+    """(array, entry point suffix): ``families`` of shape (ncol,) are table families, of shape (ncol, 2) pairs (a, b)."""
+    fam = np.ascontiguousarray(families, dtype=np.int32)
+    if fam.ndim == 2:
+        if fam.shape != (ncol, 2):
+            raise ValueError(f"families: expected {ncol} pairs (a, b), got shape {fam.shape}")
+        return fam, "_spin"
+    return _index(fam, ncol, "families"), ""
+
+
 def cl2corr_columns(a, families, lmax, out=None):
     """xi[c][k] = sum_l (2l + 1) / 4 pi a[c][l] T_f[l][k] at the lmax + 1 Gauss-Legendre nodes for a batch of columns ``a`` (ncol, nl),
     column c tied to table family ``families[c]`` (0: P_l, 1: d^l_22, 2: d^l_2-2, 3: d^l_20; l from 2 for the last three): one FP64 GEMM per
     family against the tables ``cl2corr`` caches.  nl = a.shape[-1] <= lmax + 1 (no zero-padding needed).  numpy arrays or contiguous
-    CUDA tensors; a tensor is used in place and the result is a tensor on its device unless ``out`` says otherwise."""
+    CUDA tensors; a tensor is used in place and the result is a tensor on its device unless ``out`` says otherwise.
+
+    ``families`` of shape (ncol, 2) ties column c to the pair (a, b) = families[c] instead: T_ab[l][k] = d^l_ab(x_k) as
+    ``wigner_d_table(lmax, a, b, x)`` gives it, l from max(|a|, |b|), for fields of any spin weight (hx_cl2corr_cols_spin; tables in
+    double-double, ``HX_XI_TABLES`` of them cached)."""
     a = _columns_in(a, "cl2corr_columns")
     ncol, nl = a.shape
-    fam = _index(families, ncol, "families")
+    fam, suffix = _families(families, ncol)
     out = _columns_out(a, (ncol, int(lmax) + 1), out)
     _lib.ensure_init()
-    _lib.check(_lib.load().hx_cl2corr_cols(int(lmax), int(nl), int(ncol), _lib.ptr(fam), _lib.ptr(a), _lib.ptr(out)))
+    fn = getattr(_lib.load(), "hx_cl2corr_cols" + suffix)
+    _lib.check(fn(int(lmax), int(nl), int(ncol), _lib.ptr(fam), _lib.ptr(a), _lib.ptr(out)))
     return out
 
 
 def corr2cl_columns(xi, families, lmax, nl=None, out=None):
     """b[c][l] = 2 pi sum_k w_k xi[c][k] T_f[l][k] for l < nl (default lmax + 1; 0 below l = 2 for families 1 .. 3) of a batch of
-    columns ``xi`` (ncol, lmax + 1): the way back of ``cl2corr_columns``, (ncol, nl)."""
+    columns ``xi`` (ncol, lmax + 1): the way back of ``cl2corr_columns``, (ncol, nl).  ``families`` of shape (ncol, 2): pairs (a, b), 0
+    below max(|a|, |b|)."""
     xi = _columns_in(xi, "corr2cl_columns")
     ncol = xi.shape[0]
     if xi.shape[1] != int(lmax) + 1:
         raise ValueError(f"corr2cl_columns: xi has {xi.shape[1]} nodes, lmax + 1 = {int(lmax) + 1}")
     nl = int(lmax) + 1 if nl is None else int(nl)
-    fam = _index(families, ncol, "families")
+    fam, suffix = _families(families, ncol)
     out = _columns_out(xi, (ncol, nl), out)
     _lib.ensure_init()
-    _lib.check(_lib.load().hx_corr2cl_cols(int(lmax), nl, int(ncol), _lib.ptr(fam), _lib.ptr(xi), _lib.ptr(out)))
+    fn = getattr(_lib.load(), "hx_corr2cl_cols" + suffix)
+    _lib.check(fn(int(lmax), nl, int(ncol), _lib.ptr(fam), _lib.ptr(xi), _lib.ptr(out)))
     return out
 
 

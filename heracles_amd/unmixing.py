@@ -81,16 +81,17 @@ def _naturalspice(wd, wm, fields, theta_max=None):
     return {key: corrected(key) for key in wd}
 
 
-def naturalspice(d, m, fields, theta_max=None):
+def naturalspice(d, m, fields, theta_max=None, exact_spin=False):
     """Natural unmixing of data spectra d by mask spectra m (heracles/unmixing.py:36-64): both go to correlation
-    functions on the mask's band limit, the ratio comes back and is cut to the data's band limit."""
+    functions on the mask's band limit, the ratio comes back and is cut to the data's band limit.  ``exact_spin``: keys with a spin
+    outside {0, 2} are transformed on the Wigner functions of their own spins instead of "like spin 2" (``transforms.cl2corr``)."""
     def band_limit(spectra):
         first = next(iter(spectra.values()))
         return first.shape[first.axis[0]]
 
     n_data, n_mask = band_limit(d), band_limit(m)
-    ratio = _naturalspice(cl2corr(_pad(d, n_mask)), cl2corr(m), fields, theta_max=theta_max)
-    return _pad(corr2cl(ratio), n_data)
+    ratio = _naturalspice(cl2corr(_pad(d, n_mask), exact_spin=exact_spin), cl2corr(m, exact_spin=exact_spin), fields, theta_max=theta_max)
+    return _pad(corr2cl(ratio, exact_spin=exact_spin), n_data)
 
 
 # ---- the same pipeline for many samples at once: columns on the matrix unit ----------------------------------------------------------
@@ -99,6 +100,9 @@ def naturalspice(d, m, fields, theta_max=None):
 # division column by column.  The combinations either side are the dict drivers' (transforms.cl2corr / corr2cl):
 #   0 x 2: a0 + a1, a0 - a1 on d20;  back (b0 + b1) / 2, (b0 - b1) / 2
 #   2 x 2: a00 + a11, a10 - a01 on d22; -a01 - a10, a00 - a11 on d2-2;  back cl00, cl11 = (b0 +- b3) / 2, cl01 = -(b1 + b2) / 2, cl10 = (b1 - b2) / 2
+# With exact_spin a column is tied to a PAIR (a, b) instead (hx_cl2corr_cols_spin; transforms.spin_pairs): (s, 0) for the two columns of
+# 0 x s, (s1, s2), (s1, s2), (s1, -s2), (s1, -s2) for the four of s1 x s2, same combinations.  Keys of spins {0, 2} keep their family
+# beside their pair (``codes``) and stay on the family path, so that they do not change a bit.
 _FAMILIES = {1: (0,), 2: (3, 3), 4: (1, 1, 2, 2)}
 
 
@@ -149,6 +153,10 @@ class SpicePlan:
     mask_families: np.ndarray
     mask_col: np.ndarray
     ndamp: np.ndarray
+    #: set where ``families`` / ``mask_families`` hold pairs (ncol, 2) (``spice_plan(exact_spin=True)`` with a spin outside {0, 2}): the
+    #: family of every column that stays on the family path (keys of spins {0, 2}), -1 for the columns that run on their pair
+    codes: np.ndarray | None = None
+    mask_codes: np.ndarray | None = None
 
     @property
     def ncol(self):
@@ -159,18 +167,32 @@ class SpicePlan:
         return len(self.mask_families)
 
 
-def spice_plan(d_spins, m_spins, fields):
+def _column_tables(spins, exact_spin):
+    """(families, codes) of the columns of ``spins`` ({key: spin}, dict order): family codes and None, or -- with ``exact_spin`` and a
+    spin outside {0, 2} among them -- pairs (ncol, 2) and the family codes of the columns that keep theirs (-1: none)."""
+    as_i32 = lambda v: np.asarray(v, dtype=np.int32)  # noqa: E731
+    fam = [f for spin in spins.values() for f in _FAMILIES[_ncols(spin)]]
+    if not (exact_spin and any(_tr._exact_key(spin) for spin in spins.values())):
+        return as_i32(fam), None
+    pairs = [p for spin in spins.values() for p in _tr.spin_pairs(spin)]
+    exact = [_tr._exact_key(spin) for spin in spins.values() for _ in range(_ncols(spin))]
+    return as_i32(pairs).reshape(-1, 2), np.where(exact, -1, as_i32(fam)).astype(np.int32)
+
+
+def spice_plan(d_spins, m_spins, fields, exact_spin=False):
     """The plan of ``naturalspice`` for data keys ``d_spins`` ({key: spin}, in dict order) and mask keys ``m_spins`` with the masks of
     ``fields``: pure host logic.  The mask of data key (a, b, i, j) is (mask_a, mask_b, i, j), found as ``_get_cl`` finds it (also as
-    (mask_b, mask_a, j, i), then with its two spin-2 axes swapped); KeyError if neither is there."""
+    (mask_b, mask_a, j, i), then with its two spin-2 axes swapped); KeyError if neither is there.
+
+    ``exact_spin``: where a data (mask) key has a spin outside {0, 2}, ``families`` (``mask_families``) are pairs (ncol, 2) and ``codes``
+    (``mask_codes``) say which columns stay on the family path; a plan of spins {0, 2} alone is the same plan with or without it."""
     mask_of = {name: f.mask for name, f in fields.items() if f.mask is not None}
-    mask_columns, mfam, c = {}, [], 0
+    mask_columns, c = {}, 0
     for mk, spin in m_spins.items():
         n = _ncols(spin)
         mask_columns[mk] = (c, n)
-        mfam.extend(_FAMILIES[n])
         c += n
-    columns, mask_key, fam, mask_col, ndamp, uses, c = {}, {}, [], [], [], {}, 0
+    columns, mask_key, mask_col, ndamp, uses, c = {}, {}, [], [], {}, 0
     for key, spin in d_spins.items():
         a, b, i, j = key
         mk = (mask_of[a], mask_of[b], i, j)
@@ -187,12 +209,13 @@ def spice_plan(d_spins, m_spins, fields):
         uses[mk] = uses.get(mk, 0) + 1
         columns[key] = (c, n)
         mask_key[key] = mk
-        fam.extend(_FAMILIES[n])
         mask_col.extend(np.broadcast_to(idx, _shape_of(spin)).ravel().tolist())  # (numpy's broadcast of data array / mask array)
         ndamp.extend([uses[mk]] * n)
         c += n
     as_i32 = lambda v: np.asarray(v, dtype=np.int32)  # noqa: E731
-    return SpicePlan(columns, mask_key, as_i32(fam), mask_columns, as_i32(mfam), as_i32(mask_col), as_i32(ndamp))
+    fam, codes = _column_tables(d_spins, exact_spin)
+    mfam, mcodes = _column_tables(m_spins, exact_spin)
+    return SpicePlan(columns, mask_key, fam, mask_columns, mfam, as_i32(mask_col), as_i32(ndamp), codes, mcodes)
 
 
 def _gpu_ops():
@@ -215,6 +238,40 @@ def _gpu_ops():
     return forward, ratio, back
 
 
+def _tile(f, ns):
+    return np.tile(f, ns) if f.ndim == 1 else np.tile(f, (ns, 1))
+
+
+def _rows(x, idx):
+    if _tr._is_tensor(x):
+        import torch
+
+        return x.index_select(0, torch.as_tensor(idx, dtype=torch.int64, device=x.device))
+    return np.ascontiguousarray(x[idx])
+
+
+def _transform(op, x, fam, codes, *args):
+    """``op(x, fam, *args)`` (forward or back) over the columns x.  Where ``fam`` holds pairs and ``codes`` names columns that keep
+    their family, those go through ``op`` with their families and the others with their pairs, two calls, and the rows are put back in
+    place: a column's result does not depend on its batch, so the split costs copies and changes no bit."""
+    if codes is None or not (codes >= 0).any():
+        return op(x, fam, *args)
+    keep, exact = np.flatnonzero(codes >= 0), np.flatnonzero(codes < 0)
+    parts = [(keep, op(_rows(x, keep), np.ascontiguousarray(codes[keep]), *args)), (exact, op(_rows(x, exact), np.ascontiguousarray(fam[exact]), *args))]
+    first = parts[0][1]
+    if _tr._is_tensor(first):
+        import torch
+
+        out = torch.empty((len(codes), first.shape[1]), dtype=first.dtype, device=first.device)
+        for idx, r in parts:
+            out.index_copy_(0, torch.as_tensor(idx, dtype=torch.int64, device=first.device), r)
+        return out
+    out = np.empty((len(codes), first.shape[1]))
+    for idx, r in parts:
+        out[idx] = r
+    return out
+
+
 def _hbm_budget():
     from .covariance import _hbm_budget as budget
 
@@ -228,7 +285,7 @@ def run_spice_plan(plan, data, num, lmax, *, den=None, x0=-5, num_per_sample=Fal
     exponent, or a function of the shared mask correlation functions that returns it.  Returns (S, plan.ncol, nl): the spectra of
     xi_data / damped xi_mask, cut at the data's band limit.
 
-    ``ops`` = (forward(a, families, lmax), ratio(xi_d, xi_num, num_col, ndamp, xi_den, den_col, x0), back(xi, families, lmax, nl));
+    ``ops`` = (forward(a, families, lmax) -- ``families`` (ncol,) family codes or (ncol, 2) pairs, as the plan has them --, ratio(xi_d, xi_num, num_col, ndamp, xi_den, den_col, x0), back(xi, families, lmax, nl));
     the default runs them on the GPU.  Samples are processed in chunks of at most ``max_columns`` data columns (default: what fits
     half of the free HBM); a column's result does not depend on its batch, so the chunking does not change a bit."""
     forward, ratio, back = ops if ops is not None else _gpu_ops()
@@ -238,8 +295,8 @@ def run_spice_plan(plan, data, num, lmax, *, den=None, x0=-5, num_per_sample=Fal
     n, ncm = lmax + 1, plan.ncol_mask
     if ncol != plan.ncol or num.shape[-2:] != (ncm, n) or (num.ndim == 3) != bool(num_per_sample):
         raise ValueError("run_spice_plan: the columns do not match the plan")
-    xi_den = forward(np.ascontiguousarray(den, dtype=np.float64), plan.mask_families, lmax) if den is not None else None
-    xi_num = None if num_per_sample else forward(num, plan.mask_families, lmax)
+    xi_den = _transform(forward, np.ascontiguousarray(den, dtype=np.float64), plan.mask_families, plan.mask_codes, lmax) if den is not None else None
+    xi_num = None if num_per_sample else _transform(forward, num, plan.mask_families, plan.mask_codes, lmax)
     if callable(x0):
         x0 = x0(xi_num)
     if max_columns is None:
@@ -252,15 +309,16 @@ def run_spice_plan(plan, data, num, lmax, *, den=None, x0=-5, num_per_sample=Fal
     for s0 in range(0, S, step):
         s1 = min(S, s0 + step)
         ns = s1 - s0
-        xi_d = forward(data[s0:s1].reshape(ns * ncol, nl), np.tile(plan.families, ns), lmax)
+        codes = None if plan.codes is None else np.tile(plan.codes, ns)
+        xi_d = _transform(forward, data[s0:s1].reshape(ns * ncol, nl), _tile(plan.families, ns), codes, lmax)
         num_col = np.tile(plan.mask_col, ns)
         if num_per_sample:
-            xi_n = forward(num[s0:s1].reshape(ns * ncm, n), np.tile(plan.mask_families, ns), lmax)
+            xi_n = _transform(forward, num[s0:s1].reshape(ns * ncm, n), _tile(plan.mask_families, ns), None if plan.mask_codes is None else np.tile(plan.mask_codes, ns), lmax)
             num_col = num_col + np.repeat(np.arange(ns, dtype=np.int32) * ncm, ncol)
         else:
             xi_n = xi_num
         xi_r = ratio(xi_d, xi_n, num_col, np.tile(plan.ndamp, ns), xi_den, np.tile(plan.mask_col, ns) if xi_den is not None else None, x0)
-        out[s0:s1] = np.asarray(back(xi_r, np.tile(plan.families, ns), lmax, nl)).reshape(ns, ncol, nl)
+        out[s0:s1] = np.asarray(_transform(back, xi_r, _tile(plan.families, ns), codes, lmax, nl)).reshape(ns, ncol, nl)
     return out
 
 
@@ -316,16 +374,16 @@ def _check_samples(samples):
     return ids, first, n
 
 
-def naturalspice_batch(samples, m, fields, theta_max=None, max_columns=None, ops=None):
+def naturalspice_batch(samples, m, fields, theta_max=None, max_columns=None, ops=None, exact_spin=False):
     """``{id: naturalspice(samples[id], fresh copy of m, fields, theta_max)}`` for samples ``{id: {key: Result}}`` that share keys and
     band limit and one mask dict ``m``: one forward GEMM over the data columns of all samples, one over the mask columns, one ratio launch
     and one GEMM back that stops at the data's band limit (in chunks of ``max_columns`` data columns when they do not fit the HBM
-    together).  ``m`` is not modified: every sample sees the undamped masks."""
+    together).  ``m`` is not modified: every sample sees the undamped masks.  ``exact_spin`` as in ``naturalspice``."""
     ids, first, n_data = _check_samples(samples)
     n_mask = _band_limit(m)
     if n_data > n_mask:
         raise ValueError("the masks' band limit is below the data's")
-    plan = spice_plan({k: tuple(r.spin) for k, r in first.items()}, {k: tuple(r.spin) for k, r in m.items()}, fields)
+    plan = spice_plan({k: tuple(r.spin) for k, r in first.items()}, {k: tuple(r.spin) for k, r in m.items()}, fields, exact_spin=exact_spin)
     x0 = -5
     if theta_max is not None:
         if _ncols(next(iter(m.values())).spin) != 1:

@@ -321,6 +321,20 @@ int hx_corr2cl(int lmax, int nspec, const double *corrs, double *cls);
  * These calls keep nothing in HBM between calls but the tables of hx_cl2corr (hx_release_caches). */
 int hx_cl2corr_cols(int lmax, int nl, int ncol, const int *family, const double *a, double *xi);
 int hx_corr2cl_cols(int lmax, int nl, int ncol, const int *family, const double *xi, double *b);
+/* The same for columns of ANY spin weight: column c is tied to the pair pairs[c] = (a, b) (host array [ncol][2]) and runs on
+ * T_{ab}[l][k] = d^l_{ab}(x_k), exactly hx_wigner_d_table(lmax, a, b) at the Gauss-Legendre nodes, with l0 = max(|a|, |b|): inputs
+ * below l0 are not read, outputs below l0 are 0, l0 > lmax or l0 >= nl gives zeros.  max(|a|, |b|) > HX_MAX_MIX_SPIN: HX_ERR_UNSUPPORTED.
+ * A spectrum of spins (s1, s2) is: (0,0) one column on T_00; one spin zero, the other s: a0 + a1, a0 - a1 on T_{s,0} (back (b0 +- b1)/2);
+ * both non-zero: a00 + a11, a10 - a01 on T_{s1,s2} and -a01 - a10, a00 - a11 on T_{s1,-s2}.  xi of a key with odd s1 - s2 changes sign
+ * with the order of the key's spins (d_{ab} = (-1)^{a-b} d_{ba}); a transform there and back does not.
+ * Tables: built in double-double (the kernel of the mixing-matrix tables, nodes with their low parts), one [lmax+1][ceil64(lmax+1)]
+ * table per NORMALISED pair (a >= |b|: (a,b), (b,a), (-b,-a), (-a,-b) share it, a pair that differs by the sign (-1)^{a-b} gets the
+ * shared table's result negated, bit for bit), 0.31 GB each at lmax 6144.  At most HX_XI_TABLES of them are kept (env, read at first
+ * use, default 8, at least 2), the one used longest ago is dropped for a new one -- also in the middle of a call whose pairs exceed
+ * the bound, which changes no bit; another lmax drops all; hx_release_caches frees them.  The family entry points above do not read
+ * these tables ((0,0), (2,2), (2,-2), (2,0) here agree with families 0 .. 3 to rounding, not to the bit).  Determinism as above. */
+int hx_cl2corr_cols_spin(int lmax, int nl, int ncol, const int *pairs, const double *a, double *xi);
+int hx_corr2cl_cols_spin(int lmax, int nl, int ncol, const int *pairs, const double *xi, double *b);
 int hx_xi_ratio(int n, int ncol, const double *xi_d, const double *xi_num, const int *num_col, const double *xi_den, const int *den_col,
                 const int *ndamp, double x0, double k, double *out);
 
