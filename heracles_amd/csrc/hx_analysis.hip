@@ -73,46 +73,94 @@ struct LegParams {
 // =====================================================================================
 // Y -> F operands:  un-pack N/S, ring phase, quadrature weight, parity combinations
 // =====================================================================================
-// grid: x = m - m0, y = tiles of 32 ring pairs; block 256 = 32 ring pairs x 8 slots.
-// Component c lives in column group c/8, slot c%8 (spin 2: field f = c/2 in group f/4).
-template <int SPIN>
-__global__ __launch_bounds__(256) void k_fourier_combine(PlanDev P, const double2 *__restrict__ Y, int ncomp, int ng,
-                                                         int ncol, int m0, int ms, const double *__restrict__ rw,
+// A work-group forms a TILE of the operand array -- TM consecutive orders of the chunk x RP ring pairs x every column of the sweep --
+// in LDS and writes it out in whole lines:
+//   1. one thread per (ring pair, m) of the tile computes RingAtM (and whether this m is pruned for the tile's ring block);
+//   2. load: a work item is (ring pair, column slot, m); the m of a tile run fastest over the lanes, in the order (m mod 4, m div 4):
+//      the spectrum of a ring pair is stored as X[4k+r] = Y_r[k], so with the tile aligned to 16 orders the four lanes of one
+//      m mod 4 read 64 contiguous bytes at either end of the spectrum (rings with 4n <= lmax wrap inside a tile and coalesce less).
+//      The finished values go to the tile at [m][ring pair][row][column], the layout of F;
+//   3. store: for a fixed m the rows of the RP ring pairs are one contiguous run of F that starts on a 128-byte line (RP rows are a
+//      multiple of 256 bytes).  The waves copy the runs 64 lanes x 16 bytes at a time: one store instruction never leaves its run.
+// Column slot s < ncol / 2: spin 0 the map c = s (2 columns at 2 s of both parity rows); spin 2 (field f = s / 2, function op = s % 2):
+// 4 columns at 4 f of row op.  Components beyond ncomp and ring pairs beyond nrp give zeros: F is never cleared.
+// Tiles: gx of TM orders (kshift: k of the chunk's first order within its tile, so that tiles start at multiples of TM in m when the
+// chunk has stride 1) x gy of RP ring pairs, numbered with the orders running fastest.  The grid is one-dimensional and an MI355X in
+// its default partition deals the work-groups round robin to its COMB_NXCD dies, each with an L2 of its own.  Tiles of neighbouring
+// orders share the 64-byte pieces that their runs of a spectrum begin and end in, so of every COMB_NXCD x COMB_XG work-groups in
+// launch order a die gets COMB_XG tiles in a row (work-group b of such a batch: tile (b % NXCD) * XG + b / NXCD of it).  TUNING ONLY:
+// the numbering is a bijection within a batch and the grid is rounded up to whole batches (the surplus returns at once), so nothing
+// but the locality depends on the die count or on how a part deals its work-groups.  Measured (raw FETCH_SIZE of
+// ten fields, which on gfx950 is probably half the bytes of these 64-byte runs and so ranks the variants but does not compare with the
+// 24.4 GB of the parent's 16-byte gathers): one contiguous span of tiles per die 11.4 GB and the slowest, launch order 24.5 GB,
+// groups of four 14.4 GB and the fastest.  Dynamic LDS: combine_lds_bytes().
+constexpr int COMB_NXCD = 8, COMB_XG = 4;    // dies the work-groups are dealt to; tiles in a row per die
+constexpr int COMB_TM = 16;                  // orders per tile
+constexpr int COMB_IPT = 3;                  // work items per thread of the load phase: sets the block size (measured: DESIGN.md section 4)
+constexpr int COMB_MPAD = 2;                 // doubles between the runs of two m in LDS (the 16 m-lanes of a work item hit 16 different 16-byte bank groups)
+// ring pairs per tile for rows of rowlen doubles.  Ten maps (16 x 8 x 320 B) and ten fields (16 x 4 x 640 B): 41 216 B of rows with the
+// padding + 6 144 B of RingAtM + 64 B of flags = 47 424 B of LDS per work-group, three work-groups per CU
+static int combine_rp(int rowlen) { return rowlen <= 40 ? 8 : 4; }
+static size_t combine_lds_bytes(int rp, int rowlen)
+{
+    return (size_t)COMB_TM * ((size_t)rp * rowlen + COMB_MPAD) * sizeof(double) + (size_t)COMB_TM * rp * sizeof(RingAtM) + COMB_TM * sizeof(int);
+}
+template <int SPIN, int RP>
+__global__ __launch_bounds__(1024) void k_fourier_combine(PlanDev P, const double2 *__restrict__ Y, int ncomp, int ncol, int m0, int ms,
+                                                         int nm, int kshift, int gx, int gy, const double *__restrict__ rw,
                                                          const LegTask *__restrict__ tasks, const MTasks *__restrict__ of_m,
                                                          double *__restrict__ F, int tile0)
 {
-    constexpr int NOP = LegCfg<SPIN>::NOP;
-    __shared__ RingAtM ring_at_m[32];
-    const int m = m0 + blockIdx.x * ms;
-    const int ty = (int)blockIdx.y + tile0;  // tile of 32 ring pairs (tile0: first tile of the slab of a StreamSweep)
-    // ring blocks in front of the first task of this m are pruned (m beyond what their rings resolve): their rows of F are
-    // never read
-    const MTasks mt = of_m[m];
-    if (mt.count == 0 || ty < tasks[mt.first].rb0) return;
-    if (threadIdx.x < 32) ring_at_m[threadIdx.x] = ring_at_m_of(P, ty * 32 + threadIdx.x, m, rw);
+    constexpr int NOP = LegCfg<SPIN>::NOP, NPAR = LegCfg<SPIN>::NPAR, TM = COMB_TM;
+    const int bq = (int)blockIdx.x / (COMB_NXCD * COMB_XG), br = (int)blockIdx.x % (COMB_NXCD * COMB_XG);
+    const int t = (bq * COMB_NXCD + br % COMB_NXCD) * COMB_XG + br / COMB_NXCD;
+    if (t >= gx * gy) return;
+    const int tx = t % gx, ty = t / gx;
+    static_assert(TM == 16 && 32 % RP == 0 && TM * RP <= 256, "tile shape");
+    extern __shared__ __align__(16) unsigned char comb_lds[];
+    const int rowlen = NPAR * NOP * ncol;         // doubles per (m, ring pair)
+    const int mstride = RP * rowlen + COMB_MPAD;  // doubles per m of the tile
+    double *tile = reinterpret_cast<double *>(comb_lds);
+    RingAtM *ring_at_m = reinterpret_cast<RingAtM *>(tile + TM * mstride);  // [ring pair][m]
+    int *m_live = reinterpret_cast<int *>(ring_at_m + TM * RP);
+    const int kb = tx * TM - kshift;                    // F row block of the tile's first order
+    const int rp0 = (ty + tile0 * (32 / RP)) * RP;      // (tile0: first 32-ring-pair block of the slab of a StreamSweep)
+    if (threadIdx.x < TM * RP) {
+        const int mi = threadIdx.x % TM, j = threadIdx.x / TM, k = kb + mi;
+        bool on = k >= 0 && k < nm;
+        if (on) {
+            // ring blocks in front of the first task of this m are pruned (m beyond what their rings resolve): their rows of F are
+            // never read
+            const int m = m0 + k * ms;
+            const MTasks mt = of_m[m];
+            on = mt.count != 0 && rp0 / 32 >= tasks[mt.first].rb0;
+            if (on) ring_at_m[j * TM + mi] = ring_at_m_of(P, rp0 + j, m, rw);
+        }
+        if (j == 0) m_live[mi] = on;
+    }
     __syncthreads();
-    const int rp = ty * 32 + (threadIdx.x >> 3);
-    const int slot = threadIdx.x & 7;
-    const bool live = rp < P.nrp;
-    const RingAtM ram = ring_at_m[threadIdx.x >> 3];
-    constexpr int NPAR = LegCfg<SPIN>::NPAR;
-    double *row = F + (((long long)blockIdx.x * P.nrp_pad + rp) * NPAR) * NOP * ncol;
-    for (int g = 0; g < ng; ++g) {
+    const int nsl = ncol >> 1;
+    for (int e = threadIdx.x; e < RP * nsl * TM; e += blockDim.x) {
+        const int i = e % TM, sj = e / TM, s = sj % nsl, j = sj / nsl;
+        const int mi = ((i & 3) << 2) | (i >> 2);
+        if (!m_live[mi]) continue;
+        const int m = m0 + (kb + mi) * ms, rp = rp0 + j;
+        const bool live = rp < P.nrp;
+        const RingAtM ram = ring_at_m[j * TM + mi];
+        double *row = tile + mi * mstride + j * rowlen;
         if (SPIN == 0) {
-            const int c = g * 8 + slot;
-            if (g * NCOL + 2 * slot >= ncol) continue;  // beyond the last (4-column) block of the row
-            double2 s = make_double2(0.0, 0.0), d = s;
+            const int c = s;
+            double2 sm = make_double2(0.0, 0.0), d = sm;
             if (live && c < ncomp) {
                 double2 fn, fs;
                 ring_modes_ns(P, Y, c, rp, m, ram, fn, fs);
-                s = cadd(fn, fs);
+                sm = cadd(fn, fs);
                 d = csub(fn, fs);
             }
-            *reinterpret_cast<double2 *>(row + g * NCOL + 2 * slot) = s;
-            *reinterpret_cast<double2 *>(row + ncol + g * NCOL + 2 * slot) = d;
+            *reinterpret_cast<double2 *>(row + 2 * s) = sm;
+            *reinterpret_cast<double2 *>(row + ncol + 2 * s) = d;
         } else {
-            const int f = g * 4 + (slot >> 1), op = slot & 1;
-            if (g * NCOL + 4 * (slot >> 1) >= ncol) continue;  // beyond the last field of the row
+            const int f = s >> 1, op = s & 1;
             double4 o0 = make_double4(0.0, 0.0, 0.0, 0.0), o1 = o0;
             if (live && 2 * f + 1 < ncomp) {
                 double2 qn, qs, un, us;
@@ -134,11 +182,49 @@ __global__ __launch_bounds__(256) void k_fourier_combine(PlanDev P, const double
                 o0 = make_double4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
                 o1 = make_double4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w);
             }
-            const int col = g * NCOL + 4 * (slot >> 1);
-            *reinterpret_cast<double4 *>(row + (0 * NOP + op) * ncol + col) = o0;
-            if (NPAR == 2) *reinterpret_cast<double4 *>(row + (1 * NOP + op) * ncol + col) = o1;
+            double2 *t0 = reinterpret_cast<double2 *>(row + (0 * NOP + op) * ncol + 4 * f);  // (16-byte pieces: the runs are 16-byte aligned)
+            t0[0] = make_double2(o0.x, o0.y);
+            t0[1] = make_double2(o0.z, o0.w);
+            if (NPAR == 2) {
+                double2 *t1 = reinterpret_cast<double2 *>(row + (1 * NOP + op) * ncol + 4 * f);
+                t1[0] = make_double2(o1.x, o1.y);
+                t1[1] = make_double2(o1.z, o1.w);
+            }
         }
     }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, npiece = RP * rowlen / 2, cpm = (npiece + 63) / 64;  // 16-byte pieces of a run, wave stores per run
+    for (int ch = threadIdx.x >> 6; ch < TM * cpm; ch += blockDim.x >> 6) {
+        const int mi = ch / cpm, u = (ch % cpm) * 64 + lane;
+        if (!m_live[mi] || u >= npiece) continue;
+        const double2 *src = reinterpret_cast<const double2 *>(tile + mi * mstride);
+        double2 *dst = reinterpret_cast<double2 *>(F + ((long long)(kb + mi) * P.nrp_pad + rp0) * rowlen);
+        dst[u] = src[u];
+    }
+}
+
+// The operand rows of the orders m0 + k ms, k < nm, for the 32-ring-pair blocks [tile0, tile0 + ntile32)
+template <int SPIN>
+static void launch_fourier_combine(hipStream_t st, const PlanDev &P, const double2 *Y, int ncomp, int ncol, int m0, int ms, int nm, const double *d_rw,
+                                   const LegTask *tasks, const MTasks *of_m, double *F, int tile0, int ntile32)
+{
+    const int kshift = ms == 1 ? m0 % COMB_TM : 0;
+    const int rowlen = LegCfg<SPIN>::NPAR * LegCfg<SPIN>::NOP * ncol;
+    const int gx = (nm + kshift + COMB_TM - 1) / COMB_TM;
+    // the widest row (two groups + two blocks of columns) in a tile of 4 ring pairs: all of combine_lds_bytes() within the 64 KiB a launch
+    // gets without asking for more -- with every parity row stored (HALF_F = 0) it is not, and this stops the build
+    static_assert((size_t)COMB_TM * (4 * LegCfg<SPIN>::NPAR * LegCfg<SPIN>::NOP * (NCOL * NGMAX + 8) + COMB_MPAD) * sizeof(double) +
+                          (size_t)COMB_TM * 4 * sizeof(RingAtM) + COMB_TM * sizeof(int) <= 65536, "a tile of 4 ring pairs must fit 64 KiB of LDS");
+    // COMB_IPT work items per thread: ten maps / ten fields are 1280 items = 448 threads, three work-groups = 21 waves per CU
+    const int rp = combine_rp(rowlen), items = rp * (ncol / 2) * COMB_TM;
+    const unsigned nt = (unsigned)std::min(1024, std::max(COMB_TM * rp, (items / COMB_IPT + 63) / 64 * 64));
+    const int gy = ntile32 * (32 / rp);
+    const dim3 grid((unsigned)((gx * gy + COMB_NXCD * COMB_XG - 1) / (COMB_NXCD * COMB_XG) * (COMB_NXCD * COMB_XG)));
+    const size_t lds = combine_lds_bytes(rp, rowlen);
+    if (rp == 8)
+        hipLaunchKernelGGL((k_fourier_combine<SPIN, 8>), grid, dim3(nt), lds, st, P, Y, ncomp, ncol, m0, ms, nm, kshift, gx, gy, d_rw, tasks, of_m, F, tile0);
+    else
+        hipLaunchKernelGGL((k_fourier_combine<SPIN, 4>), grid, dim3(nt), lds, st, P, Y, ncomp, ncol, m0, ms, nm, kshift, gx, gy, d_rw, tasks, of_m, F, tile0);
 }
 
 // =====================================================================================
@@ -878,9 +964,8 @@ static int launch_chunk(hx_plan *pl, hx_plan::SpinData &sd, hx_plan::TaskSet &ts
     const int ms = std::max(pl->m_step, 1), nm = (m1 - m0 + ms - 1) / ms;  // the orders m0 + k ms < m1
     {
         ProfScope ps("fourier_combine");
-        dim3 grid(nm, pl->nrp_pad / 32);
-        hipLaunchKernelGGL(k_fourier_combine<SPIN>, grid, dim3(256), 0, st, P, pl->Y.as<double2>(), nb, ng, ncol, m0, ms, d_rw,
-                           ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->F.as<double>(), 0);
+        launch_fourier_combine<SPIN>(st, P, pl->Y.as<double2>(), nb, ncol, m0, ms, nm, d_rw, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
+                                     pl->F.as<double>(), 0, pl->nrp_pad / 32);
     }
     if (t1 > t0) {
         ProfScope ps("legendre_analysis");
@@ -1118,9 +1203,8 @@ static int stream_slab(StreamSweep &s, int k)
     {
         ProfScope ps("fourier_combine");
         const int tile_hi = k + 1 == s.nslab ? pl->nrp_pad / 32 : rp_hi / 32;  // (the padding rows behind the last ring pair are zeroed with the last slab)
-        dim3 grid(nm, tile_hi - rp_lo / 32);
-        hipLaunchKernelGGL(k_fourier_combine<SPIN>, grid, dim3(256), 0, st, P, pl->Y.as<double2>(), s.nb, ng, sh.ncol, 0, 1, s.d_rw,
-                           ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(), pl->F.as<double>(), rp_lo / 32);
+        launch_fourier_combine<SPIN>(st, P, pl->Y.as<double2>(), s.nb, sh.ncol, 0, 1, nm, s.d_rw, ts.d_tasks.as<LegTask>(), ts.d_of_m.as<MTasks>(),
+                                     pl->F.as<double>(), rp_lo / 32, tile_hi - rp_lo / 32);
     }
     {
         ProfScope ps("legendre_analysis");
