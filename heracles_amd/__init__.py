@@ -23,7 +23,7 @@ from .covariance import (
     shrinkage_factor,
 )
 from .core import DeviceArray, Result, TocDict, toc_match, update_metadata
-from .discrete import HipDiscreteMapper, PointSHT, alm_resample, get_point_sht
+from .discrete import HipDiscreteMapper, PointField, PointSHT, alm_resample, get_point_sht
 from .jackknife import RegionAlms, correct_footprint_naturalspice_batch, jackknife_cls, region_alms
 from .mapper import HipHealpixMapper
 from .catalog import ArrayCatalog, CatalogView, FootprintFilter, InvalidValueFilter
@@ -62,7 +62,7 @@ from .twopoint import (
 from .unmixing import naturalspice, naturalspice_batch
 
 __all__ = [
-    "HipHealpixMapper", "HipDiscreteMapper", "PointSHT", "get_point_sht", "alm_resample", "Plan", "get_plan", "HxError", "init", "device_count", "synchronize",
+    "HipHealpixMapper", "HipDiscreteMapper", "PointSHT", "PointField", "get_point_sht", "alm_resample", "Plan", "get_plan", "HxError", "init", "device_count", "synchronize",
     "alm2cl", "alm2cl_pairs", "alm2lmax", "angular_power_spectra", "debias_cls",
     "mixing_matrices", "mixmat", "mixmat_eb", "cl2corr", "corr2cl", "gauss_legendre",
     "wigner_d_table", "naturalspice", "naturalspice_batch", "cl2corr_columns", "corr2cl_columns", "correct_footprint_naturalspice_batch", "Result", "TocDict", "toc_match", "update_metadata", "DeviceArray",

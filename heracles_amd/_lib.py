@@ -30,6 +30,7 @@ SYMBOLS = (
     "hx_alm2cl_pairs", "hx_alm2cl_pairs_range", "hx_gauss_legendre", "hx_gauss_legendre_dd", "hx_wigner_d_table", "hx_mixmat",
     "hx_mixmat_eb", "hx_mixmat_eb_spin", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_apply_spin", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_mixctx_apply_binned_spin", "hx_cl2corr", "hx_corr2cl", "hx_cl2corr_cols", "hx_corr2cl_cols", "hx_cl2corr_cols_spin", "hx_corr2cl_cols_spin", "hx_xi_ratio", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64", "hx_fits_unpack_columns",
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
+    "hx_pointsht_synthesis", "hx_pointsht_grids", "hx_pointgrid_gather", "hx_pointgrid_destroy",
     "hx_pixel_weights_size", "hx_pixel_weights_expand",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
@@ -138,6 +139,12 @@ def load():
         L.hx_pointsht_destroy.restype = None
         L.hx_pointsht_info.argtypes = [vp, C.POINTER(C.c_int)]
         L.hx_pointsht_adjoint.argtypes = [vp, i, i, C.c_int64, dp, dp, dp]
+        L.hx_pointsht_synthesis.argtypes = [vp, i, i, C.c_int64, dp, dp, dp]
+        L.hx_pointsht_grids.argtypes = [vp, i, i, dp]
+        L.hx_pointsht_grids.restype = vp
+        L.hx_pointgrid_gather.argtypes = [vp, C.c_int64, dp, dp]
+        L.hx_pointgrid_destroy.argtypes = [vp]
+        L.hx_pointgrid_destroy.restype = None
         L.hx_ring_modes_size.argtypes = [vp, i]
         L.hx_ring_modes_size.restype = C.c_int64
         L.hx_ring_modes.argtypes = [vp, i, dp, dp, dp, i, vp, vp, i, vp]

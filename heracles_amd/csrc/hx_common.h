@@ -150,5 +150,15 @@ using GridOf = std::function<int(int c, const double **grid)>;
 int pointsht_order(hx_pointsht *ps, int64_t npoints, const double2 *loc, PointOrder *o);
 int pointsht_spread_one(hx_pointsht *ps, const PointOrder &o, int64_t npoints, const double2 *loc, const double *val, double *grid);
 int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &grid_of, double2 *d_alm);
+// The two halves of hx_pointsht_synthesis, the forward direction (alm -> values at the points), for callers that keep grids resident
+// (hx_pointgrid).  Half one does not depend on the points: pointsht_alm_to_grids runs the Legendre synthesis sweeps and the three
+// transposed FFT stages; component c's grid [n1][n1] is written where grid_for(c) says, and grid_done(c, grid) (may be empty) is called
+// once its stages are queued -- a caller with one grid gathers from it there.  d_alm: [ncomp][nlm] on the device.
+// Half two: pointsht_gather_one reads one component at n points, ordered by pointsht_order as for the spread (the same tile rule):
+// val[n], NaN at points outside the sphere, which are counted in the object's nbad.
+using GridFor = std::function<int(int c, double **grid)>;
+using GridDone = std::function<int(int c, const double *grid)>;
+int pointsht_alm_to_grids(hx_pointsht *ps, int spin, int ncomp, const double2 *d_alm, const GridFor &grid_for, const GridDone &grid_done);
+int pointsht_gather_one(hx_pointsht *ps, const PointOrder &o, int64_t npoints, const double2 *loc, const double *grid, double *val);
 
 }  // namespace hx

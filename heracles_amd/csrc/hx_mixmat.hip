@@ -695,7 +695,7 @@ static WigSeed wigner_seed(int a, int b)
     sd.pm = A - B;
     unsigned __int128 bin = 1;
     for (int i = 1; i <= sd.pm; ++i) bin = bin * (unsigned)(sd.pp + i) / (unsigned)i;
-    const long double c = sqrtl((long double)(unsigned long long)bin);
+    const long double c = sqrtl((long double)bin);  // (not through 64 bits: C(2A, A) passes 2^64 at A = 34, the polar tables of hx_nufft.hip go to 56)
     sd.ch = (double)c;
     sd.cl = (double)(c - (long double)sd.ch);
     const char *e = getenv("HX_WIGNER_SEED");

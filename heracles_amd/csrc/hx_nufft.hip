@@ -29,9 +29,13 @@
 // (hx_mapper.hip) keeps one grid per component resident over the pages of a catalogue and runs half two once at the end.
 // The spread adds with hardware float64 atomics (global, and LDS in the tile kernel), whose order is not fixed: results agree from run
 // to run to rounding, NOT bit for bit.
+// The forward direction, alm -> values at the points (hx_pointsht_synthesis, hx_pointgrid_*), is the same chain transposed; it is
+// described where its kernels start, below k_nufft_fft.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <memory>
 
 #include "hx_sht_common.h"
 
@@ -45,6 +49,10 @@ struct hx_pointsht {
     double beta = 0.0, epsilon = 0.0;
     hx_plan *eq = nullptr;
     hx::DevBuf tw, dec_phi, fac_theta, grid, T, U, h, nbad, key, key2, idx, idx2, sort_tmp;
+    // forward direction: the rings next to the poles (k_polar_modes), nodes x + xlo and one Wigner-d table per spin weight
+    int polar_K = 0, polar_M = 0;
+    hx::DevBuf polar_x, polar_xlo;
+    std::map<int, std::unique_ptr<hx::DevBuf>> polar_tab;
 };
 
 namespace hx {
@@ -256,6 +264,291 @@ __global__ __launch_bounds__(512) void k_nufft_fft(NufftFft a)
     }
 }
 
+// ---- the forward direction: alm -> values at the points (ducc0's synthesis_general) -----------------------------------------------
+//     v_p = Re sum_m c_m F_m(theta_p) exp(i m phi_p),   F_m(theta) = sum_l a_lm lambda_lm(theta),   c_0 = 1, c_m = 2,
+// is the transpose of the chain above, stage by stage (a type-2 non-uniform FFT):
+//   0. the Legendre synthesis sweeps of alm2map (hx_legendre_valu.hip) on the equiangular plan: ring modes Fv[m][ring pair] = F_m at
+//      theta_r (N) and pi - theta_r (S); ring j = r is N, ring j = N/2 - 1 - r is S, and F_m(theta_{N-1-j}) = (-1)^(m+s) F_m(theta_j)
+//      continues them to the full circle (the transpose of the fold in ring_modes_ns, hx_sht_common.h);
+//   1. F_m is a trigonometric polynomial of degree <= lmax and N > 2 lmax, so ONE forward FFT of length N gives its coefficients
+//      exactly: f(k, m) = (1/N) sum_j F_m(theta_j) exp(-i k theta_j) = X[k mod N] exp(-i pi k / N) / N; divided by psi^(k):
+//      U[m][k mod N] = X[k mod N] conj(fac[k]) / N;
+//   2. zero-padded inverse FFT of length n1: T[m][a] = sum_k U[m][k] exp(2 pi i k a / n1), kept for the band of rows a point reads;
+//   3. per band row, inverse FFT of length n1 over m with c_m dec[m], real part: the grid row g[a][.];
+//   4. gather: v_p = sum_{a, b < W} psi(i0 + a - x_p) psi(j0 + b - y_p) g[i0 + a][j0 + b], corner (i0, j0) of nufft_corner.
+// Nothing is added to memory that another thread adds to: a call's result is bit-identical from run to run.
+// n1 is a power of two (2 N, N = 16 * 2^k): indices wrap with a mask here.
+struct NufftSyn {
+    const double *Fv;       // MODE 0: ring modes [m][nrp_pad][nv], component c = (N_re, N_im, S_re, S_im) at 4 c
+    const double2 *src;     // MODE 1: U, MODE 2: T
+    double2 *dst;           // MODE 0: U, MODE 1: T
+    double *grid;           // MODE 2
+    const double *dec;      // MODE 2: 1 / psi^(m)
+    const double2 *fac;     // MODE 0: exp(i pi k / N) / psi^(k), index k + lmax
+    const double2 *tw;
+    long long mstride;      // MODE 0: doubles between two orders of Fv
+    int nv, comp4, parity;  // MODE 0: doubles per ring pair, 4 c, spin weight & 1
+    int n, lmax, N, n1, row0, band, twN;
+};
+
+// One work-group per row, the R x 8192 split of k_nufft_fft.  Inverse transforms: conjugate in, conjugate out.
+// MODE 0: ring modes of order m = blockIdx.x, continued to N rings -> U[m][k mod N], |k| <= lmax
+// MODE 1: row m of U, zero-padded to n1, inverse -> T[m][a], a in the band
+// MODE 2: band row a = (row0 + blockIdx.x) mod n1: c_m dec[m] T[m][a], zero beyond lmax, inverse, real part -> grid[a][.]
+template <int MODE>
+__global__ __launch_bounds__(512) void k_nufft_fft_syn(NufftSyn a)
+{
+    extern __shared__ double2 buf[];
+    __shared__ double2 tw_hi[TW_HI_MAX], tw_lo[64];
+    const TwFactored twf = load_tw_factored(tw_hi, tw_lo, a.tw, a.twN);
+    const int n = a.n;
+    const int R = n > NUFFT_LDS_MAX ? n / NUFFT_LDS_MAX : 1, ns = n / R, p = ilog2(ns);
+    const int row = MODE == 2 ? (a.row0 + (int)blockIdx.x) & (a.n1 - 1) : (int)blockIdx.x;
+    auto input = [&](int e) -> double2 {
+        if (MODE == 0) {
+            const bool second = 2 * e >= a.N;          // theta_e = 2 pi - theta_j
+            const int j = second ? a.N - 1 - e : e;
+            const bool south = 4 * j >= a.N;           // theta_j = pi - theta_rp
+            const int rp = south ? a.N / 2 - 1 - j : j;
+            const double2 v = reinterpret_cast<const double2 *>(a.Fv + (long long)row * a.mstride + (long long)rp * a.nv + a.comp4)[south ? 1 : 0];
+            return (second && ((row + a.parity) & 1)) ? mk(-v.x, -v.y) : v;
+        } else if (MODE == 1) {
+            if (e <= a.lmax) return cconj(a.src[(long long)row * a.N + e]);
+            if (e >= n - a.lmax) return cconj(a.src[(long long)row * a.N + (e - n + a.N)]);
+            return mk(0.0, 0.0);
+        } else {
+            if (e > a.lmax) return mk(0.0, 0.0);
+            return cconj(cscale(a.src[(long long)e * a.n1 + row], (e ? 2.0 : 1.0) * a.dec[e]));
+        }
+    };
+    for (int r = 0; r < R; ++r) {
+        __syncthreads();  // twiddle tables written / previous sub-transform read out
+        for (int j = threadIdx.x; j < ns; j += blockDim.x) {
+            double2 t = mk(0.0, 0.0);
+            for (int q = 0; q < R; ++q) t = cadd(t, rot4(input(j + q * ns), (4 / R) * q * r));
+            if (r && j) t = cmul(t, expipi(-2.0 * (double)(((long long)j * r) % n) / (double)n));
+            buf[lds_slot(j)] = t;
+        }
+        __syncthreads();
+        lds_fft_dif(buf, ns, twf, a.twN);
+        for (int k = threadIdx.x; k < ns; k += blockDim.x) {
+            const int idx = R * k + r;
+            const double2 v = buf[lds_slot(bitrev(k, p))];
+            if (MODE == 0) {
+                int kk;
+                if (idx <= a.lmax) kk = idx;
+                else if (idx >= n - a.lmax) kk = idx - n;
+                else continue;
+                a.dst[(long long)row * a.N + idx] = cscale(cmul(v, cconj(a.fac[kk + a.lmax])), 1.0 / a.N);
+            } else if (MODE == 1) {
+                if (((idx - a.row0) & (a.n1 - 1)) < a.band) a.dst[(long long)row * a.n1 + idx] = cconj(v);
+            } else {
+                a.grid[(long long)row * a.n1 + idx] = v.x;
+            }
+        }
+    }
+}
+
+// One thread per point: 2 W kernel values, W x W reads of the grid.  A point outside the sphere is counted and reads NaN.
+__global__ __launch_bounds__(256) void k_nufft_gather(long long npts, const double2 *__restrict__ loc, const double *__restrict__ grid,
+                                                      double *__restrict__ val, int n1, int W, double beta,
+                                                      unsigned long long *__restrict__ nbad)
+{
+    const double inv_hw = 2.0 / W;
+    const int mask = n1 - 1;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < npts; p += (long long)gridDim.x * blockDim.x) {
+        double x, y;
+        long long i0, j0;
+        if (!nufft_corner(loc[p], n1, W, x, y, i0, j0)) {
+            atomicAdd(nbad, 1ULL);
+            val[p] = __builtin_nan("");
+            continue;
+        }
+        double wj[NUFFT_WMAX];
+        int jj[NUFFT_WMAX];
+#pragma unroll
+        for (int b = 0; b < NUFFT_WMAX; ++b) {
+            wj[b] = b < W ? es_kernel((double)(j0 + b) - y, inv_hw, beta) : 0.0;
+            jj[b] = (int)(j0 + b) & mask;
+        }
+        double s = 0.0;
+        for (int a = 0; a < W; ++a) {
+            const double wa = es_kernel((double)(i0 + a) - x, inv_hw, beta);
+            const double *row = grid + (long long)((int)(i0 + a) & mask) * n1;
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < NUFFT_WMAX; ++b)
+                if (b < W) t = fma(wj[b], row[jj[b]], t);
+            s = fma(wa, t, s);
+        }
+        val[p] = s;
+    }
+}
+
+// Points in the tile order of pointsht_order (the keys and the sort of the spread): one work-group per occupied 64 x 64 tile loads the
+// (64 + 15)-row window its points read into LDS with coalesced row reads (50 KB) and gathers from there; block `ntiles` writes NaN for
+// the invalid points, which sort behind every tile (k_nufft_keys has counted them).  A tile of at most NUFFT_TSPARSE points skips the
+// window (10^6 points at lmax 6144 are 8 per tile: loading 131 000 windows took 5.2 ms where one thread per point takes 2.1).  All
+// three ways form the same sums in the same order: a point's value does not depend on the path or on its neighbours.
+constexpr int NUFFT_TSPARSE = 256 / NUFFT_WMAX;  // one (point, window row) per thread of the group
+__global__ __launch_bounds__(256) void k_nufft_gather_tiles(long long npts, const double2 *__restrict__ loc, const unsigned *__restrict__ key,
+                                                            const unsigned *__restrict__ idx, const double *__restrict__ grid,
+                                                            double *__restrict__ val, int n1, int W, double beta, int ntx, unsigned ntiles)
+{
+    __shared__ double tile[NUFFT_TW * NUFFT_TLD];
+    __shared__ long long seg[2];
+    const unsigned me = blockIdx.x;
+    const bool bad = me == ntiles;
+    if (threadIdx.x < 2) {  // first sorted position with key >= me (+ 1)
+        const unsigned want = bad ? 0xffffffffu : me + threadIdx.x;
+        long long lo = 0, hi = npts;
+        if (bad && threadIdx.x) lo = npts;
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (key[mid] < want) lo = mid + 1;
+            else hi = mid;
+        }
+        seg[threadIdx.x] = lo;
+    }
+    __syncthreads();
+    const long long p0 = seg[0], p1 = seg[1];
+    if (p0 == p1) return;
+    if (bad) {
+        for (long long q = p0 + threadIdx.x; q < p1; q += blockDim.x) val[idx[q]] = __builtin_nan("");
+        return;
+    }
+    const int mask = n1 - 1;
+    const int ti0 = (int)(me / ntx) * NUFFT_TS - NUFFT_TPAD, tj0 = (int)(me % ntx) * NUFFT_TS - NUFFT_TPAD;
+    const double inv_hw = 2.0 / W;
+    if (p1 - p0 <= NUFFT_TSPARSE) {
+        // a sparse tile reads the grid itself, W^2 cells per point against the 79 x 79 of the window: thread (point q, c) of the 16 x 16
+        // forms the kernel values psi(j0 + c - y), psi(i0 + c - x) once, then the sum of window row c, and thread (q, 0) adds the rows
+        double *wjs = tile, *was = tile + NUFFT_TSPARSE * NUFFT_WMAX, *ts = tile + 2 * NUFFT_TSPARSE * NUFFT_WMAX;
+        const int q = threadIdx.x / NUFFT_WMAX, c = threadIdx.x % NUFFT_WMAX, o = q * NUFFT_WMAX;
+        const bool live = q < (int)(p1 - p0);
+        const unsigned p = live ? idx[p0 + q] : 0u;
+        double x = 0.0, y = 0.0;
+        long long i0 = 0, j0 = 0;
+        if (live) {
+            nufft_corner(loc[p], n1, W, x, y, i0, j0);
+            wjs[o + c] = c < W ? es_kernel((double)(j0 + c) - y, inv_hw, beta) : 0.0;
+            was[o + c] = c < W ? es_kernel((double)(i0 + c) - x, inv_hw, beta) : 0.0;
+        }
+        __syncthreads();
+        if (live && c < W) {
+            const double *row = grid + (long long)((int)(i0 + c) & mask) * n1;
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < NUFFT_WMAX; ++b)
+                if (b < W) t = fma(wjs[o + b], row[(int)(j0 + b) & mask], t);
+            ts[o + c] = t;
+        }
+        __syncthreads();
+        if (live && c == 0) {
+            double s = 0.0;
+            for (int a = 0; a < W; ++a) s = fma(was[o + a], ts[o + a], s);
+            val[p] = s;
+        }
+        return;
+    }
+    for (int c = threadIdx.x; c < NUFFT_TW * NUFFT_TLD; c += blockDim.x) {
+        const int r = c / NUFFT_TLD, cc = c % NUFFT_TLD;
+        tile[c] = cc < NUFFT_TW ? grid[(long long)((ti0 + r) & mask) * n1 + ((tj0 + cc) & mask)] : 0.0;
+    }
+    __syncthreads();
+    for (long long q = p0 + threadIdx.x; q < p1; q += blockDim.x) {
+        const unsigned p = idx[q];
+        double x, y;
+        long long i0, j0;
+        nufft_corner(loc[p], n1, W, x, y, i0, j0);
+        double wj[NUFFT_WMAX];
+#pragma unroll
+        for (int b = 0; b < NUFFT_WMAX; ++b) wj[b] = b < W ? es_kernel((double)(j0 + b) - y, inv_hw, beta) : 0.0;
+        const double *base = tile + ((int)i0 - ti0) * NUFFT_TLD + ((int)j0 - tj0);
+        double s = 0.0;
+        for (int a = 0; a < W; ++a) {  // (the same sums in the same order on both branches, and in k_nufft_gather)
+            const double wa = es_kernel((double)(i0 + a) - x, inv_hw, beta);
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < NUFFT_WMAX; ++b)
+                if (b < W) t = fma(wj[b], base[a * NUFFT_TLD + b], t);
+            s = fma(wa, t, s);
+        }
+        val[p] = s;
+    }
+}
+
+// ---- ring modes next to the poles ------------------------------------------------------------------------------------------------------
+// The Legendre sweeps run their three-term recursion through x = cos(theta) in float64.  On a ring next to a pole that x fixes theta to
+// 1.1e-16 / sin(theta) only, and the error is the same at every l: l * 1.1e-16 / sin(theta_ring) of a value, 4e-11 of the largest value
+// at lmax 4200 (theta_0 = pi / N = 1.9e-4) for a point that lies among those rings.  The adjoint lives with it (its tests give such points a
+// wider bound); here the modes of the NUFFT_POLAR_K ring pairs next to the poles are formed again from Wigner-d tables built in
+// double-double at the nodes x + xlo (wigner_table_build, hx_mixmat.hip: the tables of the mixing matrices), for the orders m <=
+// NUFFT_POLAR_M, and overwrite what the sweep left:
+//     (+-s)lambda_lm(theta) = (-1)^m N_l d^l_{m,-+s}(theta),  N_l = sqrt((2l+1)/4pi)     (s = 0: lambda_lm = (-1)^m N_l d^l_{m0}),
+//     P+ = -(-1)^m sum_l N_l d^l_{m,-s} (E + iB),  P- = -(-1)^(m+s) sum_l N_l d^l_{m,+s} (E - iB),  Q = (P+ + P-) / 2,  U = (P+ - P-) / 2i,
+// with the tables' d^l_{ab} (seed d^A_{AB} > 0 for A >= |B|: (-1)^(a-b) times the d^j_{m'm} of the textbooks) and the convention of the
+// sweeps for (E, B) -> (Q, U) (tests/spin_synthesis_reference.py writes it out).  Ring pair r >= K carries at most 1 / (2K + 1) of the
+// first ring's error; on these rings l theta <= pi (K - 1/2) = 23.6 (N > 2 lmax), where an order beyond 48 is below 2e-10 of the largest
+// value (lambda_lm ~ J_m(l theta) <= (l theta / 2)^m / m!), and the sweep's relative error of 1e-9 of that is nothing.  The table of a weight is built when the weight is first
+// used: 2 (M + 1) (lmax + 1) 2K doubles, 71 MB at lmax 6144.  One wave per (order, ring, map / field): lane j adds the l = l0 + j mod 64,
+// the lanes are added in a fixed order.
+// Weights beyond NUFFT_POLAR_SMAX keep the sweep's modes: the seeds of those tables take a binomial the host forms in 128 bits.
+constexpr int NUFFT_POLAR_K = 8, NUFFT_POLAR_M = 48, NUFFT_POLAR_SMAX = 56;
+struct PolarModes {
+    const double *tab;    // [m][1 or 2][lmax + 1][2K]: d^l_{m,-s}, then (s > 0) d^l_{m,+s}, at the nodes k < K north, K + r south
+    const double2 *alm;   // first component of the sweep
+    double *Fv;
+    long long nlm, mstride;
+    int lmax, s, K, nv;
+};
+__global__ __launch_bounds__(64) void k_polar_modes(PolarModes a)
+{
+    const int m = blockIdx.x, k = blockIdx.y, u = blockIdx.z, lane = threadIdx.x;
+    const int s = a.s, n2 = 2 * a.K, l0 = max(m, s);
+    const long long cb = (long long)m * (2 * a.lmax + 1 - m) / 2, tsize = (long long)(a.lmax + 1) * n2;
+    const double *tp = a.tab + (long long)m * (s ? 2 : 1) * tsize + k, *tm = tp + tsize;
+    const double2 *E = a.alm + (long long)(s ? 2 * u : u) * a.nlm + cb, *B = E + a.nlm;
+    double pr = 0.0, pi = 0.0, mr = 0.0, mi = 0.0;
+    for (int l = l0 + lane; l <= a.lmax; l += 64) {
+        const double nl = sqrt((2.0 * l + 1.0) * (0.25 / M_PI));
+        const double2 e = E[l];
+        if (s == 0) {
+            const double d = nl * tp[(long long)l * n2];
+            pr = fma(d, e.x, pr);
+            pi = fma(d, e.y, pi);
+        } else {
+            const double2 b = B[l];
+            const double dp = nl * tp[(long long)l * n2], dm = nl * tm[(long long)l * n2];
+            pr = fma(dp, e.x - b.y, pr);  // E + iB
+            pi = fma(dp, e.y + b.x, pi);
+            mr = fma(dm, e.x + b.y, mr);  // E - iB
+            mi = fma(dm, e.y - b.x, mi);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        pr += __shfl_xor(pr, o);
+        pi += __shfl_xor(pi, o);
+        mr += __shfl_xor(mr, o);
+        mi += __shfl_xor(mi, o);
+    }
+    if (lane) return;
+    const bool south = k >= a.K;
+    double *row = a.Fv + (long long)m * a.mstride + (long long)(south ? k - a.K : k) * a.nv + (south ? 2 : 0);
+    const double sgm = (m & 1) ? -1.0 : 1.0;
+    if (s == 0) {
+        row[4 * u] = sgm * pr;
+        row[4 * u + 1] = sgm * pi;
+        return;
+    }
+    const double sgs = (s & 1) ? sgm : -sgm;  // -(-1)^(m + s)
+    const double ppr = -sgm * pr, ppi = -sgm * pi, pmr = sgs * mr, pmi = sgs * mi;
+    row[8 * u] = 0.5 * (ppr + pmr);
+    row[8 * u + 1] = 0.5 * (ppi + pmi);
+    row[8 * u + 4] = 0.5 * (ppi - pmi);
+    row[8 * u + 5] = -0.5 * (ppr - pmr);
+}
+
 // Gauss-Legendre nodes on [-1, 1] (host, Newton on P_n)
 static void gl_nodes(int n, std::vector<double> &x, std::vector<double> &w)
 {
@@ -328,6 +621,9 @@ extern "C" hx_pointsht *hx_pointsht_create(int lmax, double epsilon)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft_syn<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft_syn<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_nufft_fft_syn<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     return ps;
 }
 
@@ -448,7 +744,250 @@ int pointsht_grids_to_alm(hx_pointsht *ps, int spin, int ncomp, const GridOf &gr
     return HX_OK;
 }
 
+// ---- the forward direction: its two halves (hx_common.h) ------------------------------------------------------------------------------
+// Half one: alm -> grids.  One sweep of the vector-unit synthesis per four maps / two spin-2 fields / one field of any other weight
+// (the sweeps of alm2map, on the equiangular plan; their ring modes live in the plan's operand buffer F, idle here as there), then per
+// component the three transposed FFT stages through the object's U and T.  Every cell a later stage reads is written by the stage
+// before it, so no buffer is cleared and an adjoint call in between (which clears what it uses) changes nothing.
+// The Wigner-d table of k_polar_modes for one spin weight, built on first use and kept by the object (only a complete table stays).
+static int polar_table(hx_pointsht *ps, int spin, const double **tab)
+{
+    const int lmax = ps->lmax;
+    if (!ps->polar_x.p || !ps->polar_xlo.p) {
+        const int K = std::min(NUFFT_POLAR_K, ps->N / 4);
+        std::vector<double> x(2 * K), xlo(2 * K);
+        for (int r = 0; r < K; ++r) {
+            const long double c = cosl(2.0L * 3.141592653589793238462643383279502884L * (r + 0.5L) / ps->N);
+            x[r] = (double)c; xlo[r] = (double)(c - (long double)x[r]);
+            x[K + r] = -x[r]; xlo[K + r] = -xlo[r];
+        }
+        HX_TRY(upload(ps->polar_x, x));
+        HX_TRY(upload(ps->polar_xlo, xlo));
+        ps->polar_K = K;
+        ps->polar_M = std::min(lmax, NUFFT_POLAR_M);
+    }
+    std::unique_ptr<DevBuf> &slot = ps->polar_tab[spin];
+    if (!slot) {
+        std::unique_ptr<DevBuf> buf(new DevBuf);
+        const int nt = spin ? 2 : 1, n2 = 2 * ps->polar_K;
+        const size_t tsize = (size_t)(lmax + 1) * n2;
+        HX_TRY(buf->alloc(sizeof(double) * tsize * nt * (ps->polar_M + 1)));
+        for (int m = 0; m <= ps->polar_M; ++m)
+            for (int t = 0; t < nt; ++t)
+                HX_TRY(wigner_table_build(lmax, m, t == 0 ? -spin : spin, n2, ps->polar_x.as<double>(), ps->polar_xlo.as<double>(),
+                                          buf->as<double>() + tsize * ((size_t)m * nt + t), n2, 1));
+        slot = std::move(buf);
+    }
+    *tab = slot->as<double>();
+    return HX_OK;
+}
+
+int pointsht_alm_to_grids(hx_pointsht *ps, int spin, int ncomp, const double2 *d_alm, const GridFor &grid_for, const GridDone &grid_done)
+{
+    hx_plan *eq = ps->eq;
+    const int lmax = ps->lmax, N = ps->N, n1 = ps->n1, W = ps->W;
+    hipStream_t st = rt().stream;
+    const int cpu = spin ? 2 : 1;
+    if (spin < 0 || ncomp < 1 || ncomp % cpu) return fail(HX_ERR_ARG, "point transform: %d components of spin %d", ncomp, spin);
+    if (spin > lmax) {  // no l >= s below the band limit: zero fields
+        for (int c = 0; c < ncomp; ++c) {
+            double *grid = nullptr;
+            HX_TRY(grid_for(c, &grid));
+            HX_HIP(hipMemsetAsync(grid, 0, sizeof(double) * (size_t)n1 * n1, st));
+            if (grid_done) HX_TRY(grid_done(c, grid));
+        }
+        return HX_OK;
+    }
+    const bool generic = analysis_generic_spin(spin);  // a spin weight other than 0 and 2 (HX_SPIN_GENERIC=1: 2 as well)
+    const int umax = generic ? 1 : synth_valu_max_units(spin);
+    HX_TRY(ps->T.alloc(sizeof(double2) * (size_t)(lmax + 1) * n1));
+    HX_TRY(ps->U.alloc(sizeof(double2) * (size_t)(lmax + 1) * N));
+    HX_TRY(eq->F.alloc(sizeof(double) * (size_t)(lmax + 1) * eq->nrp_pad * 4 * std::min(umax * cpu, ncomp)));
+    const double *polar = nullptr;
+    if (spin <= NUFFT_POLAR_SMAX) HX_TRY(polar_table(ps, spin, &polar));
+    NufftSyn a;
+    a.Fv = eq->F.as<double>(); a.grid = nullptr; a.src = nullptr; a.dst = nullptr;
+    a.dec = ps->dec_phi.as<double>(); a.fac = ps->fac_theta.as<double2>(); a.tw = ps->tw.as<double2>();
+    a.parity = spin & 1;
+    a.lmax = lmax; a.N = N; a.n1 = n1; a.twN = ps->twN;
+    a.band = std::min(n1, n1 / 2 + W + 4);  // rows a point with 0 <= theta <= pi can read
+    a.row0 = (n1 - W / 2 - 2) % n1;
+    auto launch = [&](int mode, int n, int rows) {
+        const int ns = std::min(n, NUFFT_LDS_MAX), threads = std::min(512, std::max(64, ns / 16));
+        a.n = n;
+        const size_t lds = (size_t)lds_fft_slots(ns) * sizeof(double2);
+        if (mode == 0) hipLaunchKernelGGL(k_nufft_fft_syn<0>, dim3(rows), dim3(threads), lds, st, a);
+        else if (mode == 1) hipLaunchKernelGGL(k_nufft_fft_syn<1>, dim3(rows), dim3(threads), lds, st, a);
+        else hipLaunchKernelGGL(k_nufft_fft_syn<2>, dim3(rows), dim3(threads), lds, st, a);
+    };
+    for (int c0 = 0; c0 < ncomp;) {
+        int units = umax;
+        while (units * cpu > ncomp - c0) units >>= 1;
+        const int nc = units * cpu;
+        hx_plan::SpinData *sd = nullptr;
+        hx_plan::TaskSet *ts = nullptr;
+        HX_TRY(spin_data(eq, spin, generic, &sd));
+        HX_TRY(task_set(eq, spin, generic, synth_valu_task_blocks(spin, units), &ts));
+        HX_TRY(launch_synth_valu(eq, spin, units, *sd, *ts, d_alm + (size_t)c0 * eq->nlm, eq->F.as<double>(), generic));
+        a.nv = 4 * nc;
+        a.mstride = (long long)eq->nrp_pad * a.nv;
+        if (polar) {
+            ProfScope pf("polar_modes");
+            PolarModes pm;
+            pm.tab = polar; pm.alm = d_alm + (size_t)c0 * eq->nlm; pm.Fv = eq->F.as<double>();
+            pm.nlm = eq->nlm; pm.mstride = a.mstride;
+            pm.lmax = lmax; pm.s = spin; pm.K = ps->polar_K; pm.nv = a.nv;
+            hipLaunchKernelGGL(k_polar_modes, dim3(ps->polar_M + 1, 2 * ps->polar_K, units), dim3(64), 0, st, pm);
+        }
+        for (int c = 0; c < nc; ++c) {
+            double *grid = nullptr;
+            HX_TRY(grid_for(c0 + c, &grid));
+            {
+                ProfScope pf("nufft_fft_syn");
+                a.comp4 = 4 * c;
+                a.dst = ps->U.as<double2>();
+                launch(0, N, lmax + 1);
+                a.src = ps->U.as<double2>(); a.dst = ps->T.as<double2>();
+                launch(1, n1, lmax + 1);
+                a.src = ps->T.as<double2>(); a.grid = grid;
+                launch(2, n1, a.band);
+                HX_HIP(hipGetLastError());
+            }
+            if (grid_done) HX_TRY(grid_done(c0 + c, grid));
+        }
+        c0 += nc;
+    }
+    return HX_OK;
+}
+
+// Half two: one component of a grid at n points.  The path is the spread's (pointsht_order): one thread per point below 300000
+// points, LDS tiles from there on.  That cross-over was measured for the spread (tools/time_pointsht.py) and is kept, so that both
+// directions share one order per call.  Measured for the gather at lmax 6144 (HX_NUFFT_TILES=0 / 1, DIRECTION=both
+// tools/time_pointsht.py; ms per component, one thread per point / tiles):
+// 10^5 0.2 / 0.9, 3 10^5 1.0 / 1.3, 10^6 2.1 / 2.1, 3 10^6 6.4 / 4.5, 10^7 19.1 / 5.6 -- its own cross-over lies near 10^6.  (With a
+// window loaded for every occupied tile the tiles took 3.2 / 4.6 / 5.2 / 5.5 / 5.9: hence the sparse branch of k_nufft_gather_tiles.)
+int pointsht_gather_one(hx_pointsht *ps, const PointOrder &o, int64_t npoints, const double2 *loc, const double *grid, double *val)
+{
+    const int n1 = ps->n1, W = ps->W;
+    hipStream_t st = rt().stream;
+    ProfScope pf("nufft_gather");
+    if (o.tiles) {
+        const int ntx = n1 / NUFFT_TS + 1, nty = (n1 / 2 + W + NUFFT_TPAD) / NUFFT_TS + 1;
+        hipLaunchKernelGGL(k_nufft_gather_tiles, dim3((unsigned)(ntx * nty) + 1), dim3(256), 0, st, (long long)npoints, loc, o.key, o.idx, grid,
+                           val, n1, W, ps->beta, ntx, (unsigned)(ntx * nty));
+    } else if (npoints > 0) {
+        const long long nblk = std::min<long long>((npoints + 255) / 256, 1 << 20);
+        hipLaunchKernelGGL(k_nufft_gather, dim3((unsigned)nblk), dim3(256), 0, st, (long long)npoints, loc, grid, val, n1, W, ps->beta,
+                           ps->nbad.as<unsigned long long>());
+    }
+    HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
 }  // namespace hx
+
+// A resident set of grids: the field of `ncomp` components of one hx_pointsht_grids call, to be read at any number of point sets.
+struct hx_pointgrid {
+    hx_pointsht *ps = nullptr;  // borrowed: tables, sort buffers, the counter of bad points
+    int ncomp = 0;
+    hx::DevBuf grids;           // [ncomp][n1][n1]
+};
+
+static int pointsht_check_bad(hx_pointsht *ps, const char *who)
+{
+    unsigned long long nbad = 0;
+    hipStream_t st = rt().stream;
+    HX_HIP(hipMemcpyAsync(&nbad, ps->nbad.p, 8, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    if (nbad) return fail(HX_ERR_ARG, "%s: %llu points with colatitude outside [0, pi] or non-finite coordinates", who, nbad);
+    return HX_OK;
+}
+
+extern "C" int hx_pointsht_synthesis(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *alm,
+                                     double *map)
+{
+    HX_TRY(ensure_ready());
+    if (!ps || !alm || (npoints > 0 && (!loc || !map))) return fail(HX_ERR_ARG, "hx_pointsht_synthesis: null argument");
+    if (spin < 0) return fail(HX_ERR_ARG, "hx_pointsht_synthesis: negative spin weight %d", spin);
+    if (ncomp < 1 || (spin > 0 && (ncomp & 1)) || npoints < 0) return fail(HX_ERR_ARG, "hx_pointsht_synthesis: bad component or point count");
+    if (npoints == 0) return HX_OK;
+    const int n1 = ps->n1;
+    InView vloc, valm;
+    OutView vmap;
+    HX_TRY(vloc.bind(loc, sizeof(double) * 2 * (size_t)npoints));
+    HX_TRY(valm.bind(alm, sizeof(double2) * (size_t)ncomp * ps->eq->nlm));
+    HX_TRY(vmap.bind(map, sizeof(double) * (size_t)ncomp * npoints));
+    hipStream_t st = rt().stream;
+    HX_TRY(ps->grid.alloc(sizeof(double) * (size_t)n1 * n1));
+    HX_HIP(hipMemsetAsync(ps->nbad.p, 0, 8, st));
+    PointOrder order;
+    HX_TRY(pointsht_order(ps, npoints, vloc.as<double2>(), &order));
+    // one grid serves every component: filled by the component's FFT stages and read right behind them
+    const GridFor one = [&](int, double **grid) -> int {
+        *grid = ps->grid.as<double>();
+        return HX_OK;
+    };
+    const GridDone read = [&](int c, const double *grid) -> int {
+        return pointsht_gather_one(ps, order, npoints, vloc.as<double2>(), grid, vmap.as<double>() + (size_t)c * npoints);
+    };
+    HX_TRY(pointsht_alm_to_grids(ps, spin, ncomp, valm.as<double2>(), one, read));
+    HX_TRY(pointsht_check_bad(ps, "hx_pointsht_synthesis"));
+    HX_TRY(vmap.finish());
+    return HX_OK;
+}
+
+extern "C" hx_pointgrid *hx_pointsht_grids(hx_pointsht *ps, int spin, int ncomp, const double *alm)
+{
+    if (ensure_ready() != HX_OK) return nullptr;
+    if (!ps || !alm || spin < 0 || ncomp < 1 || (spin > 0 && (ncomp & 1))) {
+        fail(HX_ERR_ARG, "hx_pointsht_grids: null argument, negative spin weight or bad component count");
+        return nullptr;
+    }
+    const size_t cells = (size_t)ps->n1 * ps->n1;
+    hx_pointgrid *g = new hx_pointgrid;
+    g->ps = ps;
+    g->ncomp = ncomp;
+    InView valm;
+    const GridFor resident = [&](int c, double **grid) -> int {
+        *grid = g->grids.as<double>() + cells * c;
+        return HX_OK;
+    };
+    if (g->grids.alloc(sizeof(double) * cells * ncomp) != HX_OK || valm.bind(alm, sizeof(double2) * (size_t)ncomp * ps->eq->nlm) != HX_OK ||
+        pointsht_alm_to_grids(ps, spin, ncomp, valm.as<double2>(), resident, GridDone()) != HX_OK ||
+        hipStreamSynchronize(rt().stream) != hipSuccess) {
+        delete g;
+        return nullptr;
+    }
+    return g;
+}
+
+extern "C" int hx_pointgrid_gather(hx_pointgrid *g, int64_t npoints, const double *loc, double *map)
+{
+    HX_TRY(ensure_ready());
+    if (!g || npoints < 0 || (npoints > 0 && (!loc || !map))) return fail(HX_ERR_ARG, "hx_pointgrid_gather: null argument or negative point count");
+    if (npoints == 0) return HX_OK;
+    hx_pointsht *ps = g->ps;
+    const size_t cells = (size_t)ps->n1 * ps->n1;
+    InView vloc;
+    OutView vmap;
+    HX_TRY(vloc.bind(loc, sizeof(double) * 2 * (size_t)npoints));
+    HX_TRY(vmap.bind(map, sizeof(double) * (size_t)g->ncomp * npoints));
+    HX_HIP(hipMemsetAsync(ps->nbad.p, 0, 8, rt().stream));
+    PointOrder order;
+    HX_TRY(pointsht_order(ps, npoints, vloc.as<double2>(), &order));
+    for (int c = 0; c < g->ncomp; ++c)
+        HX_TRY(pointsht_gather_one(ps, order, npoints, vloc.as<double2>(), g->grids.as<double>() + cells * c, vmap.as<double>() + (size_t)c * npoints));
+    HX_TRY(pointsht_check_bad(ps, "hx_pointgrid_gather"));
+    HX_TRY(vmap.finish());
+    return HX_OK;
+}
+
+extern "C" void hx_pointgrid_destroy(hx_pointgrid *g)
+{
+    if (!g) return;
+    if (rt().ready) (void)hipStreamSynchronize(rt().stream);
+    delete g;
+}
 
 extern "C" int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *map,
                                    double *alm)

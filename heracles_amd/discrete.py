@@ -5,7 +5,9 @@
 ``resample`` re-packs on the GPU through ``hx_alm_resample``.  ``map_values`` -- ducc0's
 non-uniform adjoint synthesis (heracles/ducc.py:92-133) -- runs through
 ``hx_pointsht_adjoint``: a type-1 non-uniform FFT on the (theta, phi) torus and the Legendre
-analysis kernel of the HEALPix path on equidistant rings (csrc/hx_nufft.hip).
+analysis kernel of the HEALPix path on equidistant rings (csrc/hx_nufft.hip).  ``sample`` is the
+way back, alms to values at points (ducc0's ``synthesis_general``), through
+``hx_pointsht_synthesis``; ``PointSHT.field`` keeps a field resident for page after page.
 """
 
 from __future__ import annotations
@@ -98,6 +100,106 @@ class PointSHT:
             raise
         return out
 
+    def _alm_arg(self, alm, spin):
+        """alm as a contiguous (ncomp, nlm) complex128 array or device tensor; ValueError for what the library would refuse."""
+        dev = hasattr(alm, "data_ptr")
+        if dev:
+            import torch
+
+            alm = alm.to(torch.complex128).contiguous()
+        else:
+            alm = np.ascontiguousarray(alm, dtype=np.complex128)
+        if alm.ndim != 2 or alm.shape[1] != self.nlm:
+            raise ValueError(f"alm must be (ncomp, {self.nlm}) for lmax {self.lmax}")
+        if int(spin) < 0 or alm.shape[0] < 1 or (int(spin) > 0 and alm.shape[0] % 2):
+            raise ValueError(f"{alm.shape[0]} components of spin {spin}")
+        return alm, dev
+
+    @staticmethod
+    def _loc_arg(loc, dev, like):
+        if dev:
+            import torch
+
+            loc = torch.as_tensor(loc, device=like.device).to(torch.float64).contiguous()
+        else:
+            loc = np.ascontiguousarray(loc, dtype=np.float64)
+        if loc.ndim != 2 or loc.shape[1] != 2:
+            raise ValueError("loc must be (npoints, 2)")
+        return loc
+
+    @staticmethod
+    def _values_out(shape, dev, like, out):
+        if out is not None:
+            return _lib.result_array(shape, out)
+        if dev:
+            import torch
+
+            return torch.empty(shape, dtype=torch.float64, device=like.device)
+        return np.empty(shape, dtype=np.float64)
+
+    def synthesis(self, loc, alm, spin=0, out=None):
+        """The forward direction (ducc0's ``synthesis_general``): alm (ncomp, nlm) complex128 -> the field's values (ncomp, npoints)
+        float64 at loc (npoints, 2) = (colatitude, longitude) [rad]; numpy in -> numpy out, torch device tensors in -> device tensor
+        out, ``out=`` is written in place and returned.  ``spin`` as for :meth:`adjoint_synthesis`: s >= 1 reads the rows in pairs
+        (E, B) and returns (Q, U) per pair (zero for s > lmax); a negative ``spin``, an odd number of rows with s >= 1 or a point
+        outside the sphere is a ``ValueError``.  Bit-identical from call to call."""
+        alm, dev = self._alm_arg(alm, spin)
+        loc = self._loc_arg(loc, dev, alm)
+        out = self._values_out((alm.shape[0], loc.shape[0]), dev, alm, out)
+        try:
+            _lib.check(_lib.load().hx_pointsht_synthesis(self._h, int(spin), int(alm.shape[0]), int(loc.shape[0]),
+                                                         _lib.ptr(loc), _lib.ptr(alm), _lib.ptr(out)))
+        except _lib.HxError as e:
+            if e.code == _lib.HX_ERR_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return out
+
+    def field(self, alm, spin=0):
+        """The field with coefficients alm, resident on the device, to be read at any number of point sets: the part of
+        :meth:`synthesis` that does not depend on the points is done once here (``ncomp`` grids of ``ngrid``^2 float64)."""
+        return PointField(self, alm, spin)
+
+
+class PointField:
+    """What ``PointSHT.field`` returns (``hx_pointgrid``): ``at(loc)`` equals ``PointSHT.synthesis(loc, alm, spin)`` bit for bit, page
+    after page, at the cost of the gather alone.  It keeps its ``PointSHT`` alive."""
+
+    def __init__(self, sht, alm, spin=0):
+        self._h = None
+        alm, _ = sht._alm_arg(alm, spin)
+        self._sht, self.spin, self.ncomp = sht, int(spin), int(alm.shape[0])
+        self._h = _lib.load().hx_pointsht_grids(sht._h, self.spin, self.ncomp, _lib.ptr(alm))
+        if not self._h:
+            raise _lib.HxError(-1, _lib.load().hx_last_error().decode(errors="replace"))
+
+    def at(self, loc, out=None):
+        """Values (ncomp, npoints) float64 at loc (npoints, 2); a numpy array unless loc or ``out`` is a device tensor."""
+        if not self._h:
+            raise ValueError("the field has been closed")
+        dev = hasattr(loc, "data_ptr") and getattr(loc, "is_cuda", False) or (out is not None and getattr(out, "is_cuda", False))
+        like = loc if hasattr(loc, "data_ptr") and getattr(loc, "is_cuda", False) else out
+        loc = PointSHT._loc_arg(loc, dev, like)
+        out = PointSHT._values_out((self.ncomp, loc.shape[0]), dev, like, out)
+        try:
+            _lib.check(_lib.load().hx_pointgrid_gather(self._h, int(loc.shape[0]), _lib.ptr(loc), _lib.ptr(out)))
+        except _lib.HxError as e:
+            if e.code == _lib.HX_ERR_ARG:
+                raise ValueError(str(e)) from None
+            raise
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().hx_pointgrid_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 _point_plans = {}
 
@@ -149,6 +251,25 @@ class HipDiscreteMapper:
         if flatten:
             alms = alms[0]
         data += alms
+
+    def sample(self, lon, lat, data, spin=0):
+        """The inverse direction of :meth:`map_values`: the values at (lon, lat) [degrees] of the field whose alms are ``data``
+        ((ncomp, nlm), or (nlm,) for one row of values), through ``PointSHT.synthesis``.  complex64 alms are evaluated to 1e-5,
+        everything else in float64 to 1e-12; alms of another band limit than the mapper's are a ``ValueError``."""
+        data = np.asarray(data)
+        flatten = data.ndim == 1
+        if flatten:
+            data = data.reshape(1, -1)
+        lmax = self.__lmax
+        if data.ndim != 2 or data.shape[1] != (lmax + 1) * (lmax + 2) // 2:
+            raise ValueError(f"alms of shape {data.shape} do not have the mapper's band limit {lmax}")
+        epsilon = 1e-5 if data.dtype == np.complex64 else 1e-12
+        lon, lat = np.asarray(lon, dtype=np.float64), np.asarray(lat, dtype=np.float64)
+        loc = np.empty((lon.size, 2), dtype=np.float64)
+        loc[:, 0] = np.radians(90.0 - lat)
+        loc[:, 1] = np.radians(lon % 360.0)
+        values = get_point_sht(lmax, epsilon).synthesis(loc, data, spin=spin)
+        return values[0] if flatten else values
 
     def transform(self, data, spin=0):
         """Does nothing, since inputs are alms already (heracles/ducc.py:135-143)."""

@@ -360,6 +360,20 @@ hx_pointsht *hx_pointsht_create(int lmax, double epsilon);
 void hx_pointsht_destroy(hx_pointsht *ps);
 int hx_pointsht_info(const hx_pointsht *ps, int *info4);
 int hx_pointsht_adjoint(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *map, double *alm);
+/* The forward direction, ducc0.sht.synthesis_general: map[c][p] = the field with coefficients alm at the point loc[p], for the same
+ * object, spins, component rules and error codes as hx_pointsht_adjoint (HX_ERR_ARG for spin < 0, an odd ncomp with spin >= 1 and for
+ * points with colatitude outside [0, pi] or non-finite coordinates, whose values are NaN).  alm: [ncomp][nlm] complex, m-major;
+ * map: [ncomp][npoints] float64; host or device; npoints == 0 is valid.  s >= 1: (E, B) pairs in, (Q, U) out; s > lmax gives zeros.
+ * Nothing is accumulated with atomics in this direction: a call's result is bit-identical from run to run.
+ * hx_pointsht_synthesis works through the one grid the object owns, component by component.  hx_pointsht_grids does the part that
+ * does not depend on the points once and keeps its result, ncomp grids of n1^2 float64 (NULL and hx_last_error when they do not fit
+ * or an argument is bad); hx_pointgrid_gather then reads all components at one set of points (map: [ncomp][npoints]) and can be
+ * called for page after page of a catalogue.  The hx_pointsht is BORROWED by the hx_pointgrid and has to outlive it.             */
+int hx_pointsht_synthesis(hx_pointsht *ps, int spin, int ncomp, int64_t npoints, const double *loc, const double *alm, double *map);
+typedef struct hx_pointgrid hx_pointgrid;
+hx_pointgrid *hx_pointsht_grids(hx_pointsht *ps, int spin, int ncomp, const double *alm);
+int hx_pointgrid_gather(hx_pointgrid *g, int64_t npoints, const double *loc, double *map);
+void hx_pointgrid_destroy(hx_pointgrid *g);
 
 /* ---- catalogue -> map accumulation (first "next" row of SURVEY.md 8f) ---------------
  * hx_ang2pix_ring replaces hp.ang2pix(nside, lon, lat, lonlat=True) at
