@@ -60,6 +60,7 @@ from .twopoint import (
     split_requests,
 )
 from .unmixing import naturalspice, naturalspice_batch
+from .weights import compute_pixel_weights
 
 __all__ = [
     "HipHealpixMapper", "HipDiscreteMapper", "PointSHT", "PointField", "get_point_sht", "alm_resample", "Plan", "get_plan", "HxError", "init", "device_count", "synchronize",
@@ -70,5 +71,5 @@ __all__ = [
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
     "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
-    "Visibility", "Weights", "get_masks",
+    "Visibility", "Weights", "get_masks", "compute_pixel_weights",
 ]

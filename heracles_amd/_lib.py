@@ -31,7 +31,7 @@ SYMBOLS = (
     "hx_mixmat_eb", "hx_mixmat_eb_spin", "hx_mixmat_batch", "hx_mixctx_create", "hx_mixctx_apply", "hx_mixctx_apply_spin", "hx_mixctx_destroy", "hx_mixctx_set_bins", "hx_mixctx_apply_binned", "hx_mixctx_apply_binned_spin", "hx_cl2corr", "hx_corr2cl", "hx_cl2corr_cols", "hx_corr2cl_cols", "hx_cl2corr_cols_spin", "hx_corr2cl_cols_spin", "hx_xi_ratio", "hx_ang2pix_ring", "hx_map_values", "hx_ud_grade", "hx_reorder", "hx_matvec", "hx_pinv", "hx_alm_resample", "hx_region_maps", "hx_alm_subtract", "hx_fits_unpack_f64", "hx_fits_pack_f64", "hx_fits_unpack_columns",
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
     "hx_pointsht_synthesis", "hx_pointsht_grids", "hx_pointgrid_gather", "hx_pointgrid_destroy",
-    "hx_pixel_weights_size", "hx_pixel_weights_expand",
+    "hx_pixel_weights_size", "hx_pixel_weights_expand", "hx_pixel_weights_solve",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
@@ -153,6 +153,7 @@ def load():
         L.hx_pixel_weights_size.argtypes = [i]
         L.hx_pixel_weights_size.restype = C.c_int64
         L.hx_pixel_weights_expand.argtypes = [i, C.c_int64, dp, dp]
+        L.hx_pixel_weights_solve.argtypes = [vp, i, C.c_double, i, dp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.hx_host_alloc.argtypes = [C.c_int64, C.POINTER(C.c_void_p)]
         L.hx_host_free.argtypes = [vp]
         L.hx_mixmat_gemm_clock.restype = C.c_double
@@ -263,7 +264,11 @@ def release_caches():
     the last sizes + host-staging buffer, ~3 GB at L = 6144), the buffers of ``alm2cl_pairs`` (<= 512 MB) and the nodes, weights and
     Wigner tables ``cl2corr`` / ``corr2cl`` / ``naturalspice`` keep for their last lmax (1.2 GB at lmax 6144; the column transforms of
     ``naturalspice_batch`` read the same tables and keep nothing of their own; with ``exact_spin`` up to ``HX_XI_TABLES`` pair tables of
-    0.31 GB each at lmax 6144 lie beside them): hx_release_caches."""
+    0.31 GB each at lmax 6144 lie beside them): hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
+    per result) go with them."""
+    from . import weights
+
+    weights.release_computed()
     check(load().hx_release_caches())
 
 

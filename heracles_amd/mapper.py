@@ -7,7 +7,9 @@ dispatch; ``transform`` runs on the GPU through libhxsht instead of ``healpy.map
 
 Data healpy ships but this repository cannot (pixel-window tables, pixel-weight files)
 is taken from the caller: pass ``pixwin=(pw_T, pw_P)`` / ``pixel_weights=...``; if they
-are omitted and the user's environment has healpy, its tables are used.
+are omitted and the user's environment has healpy, its tables are used.  The pixel weights
+need no file: ``pixel_weights="compute"`` solves for them on the GPU on the first transform
+(heracles_amd/weights.py, ``compute_pixel_weights``).
 """
 
 from __future__ import annotations
@@ -60,7 +62,9 @@ def _warn_unit_weights():
     """One-time note: the reference calls hp.map2alm(use_pixel_weights=True, datapath=DATAPATH); the weight
     files are healpy data this package cannot ship, so without ``pixel_weights`` / ``ring_weights`` the
     quadrature uses unit weights (+ ``niter`` Jacobi iterations) and differs from the reference at the level of
-    the HEALPix quadrature error (~1e-3 relative at l ~ 2 nside without iterations, ~1e-5 with niter=3)."""
+    the HEALPix quadrature error (~1e-3 relative at l ~ 2 nside without iterations, ~1e-5 with niter=3).
+    ``pixel_weights="compute"`` needs no file: the weights are solved for on the GPU (heracles_amd/weights.py), pinned by the
+    exact round trip ``map2alm(alm2map(a), niter=0) == a`` for ``lmax <= 3 * nside // 2``, and no note is issued."""
     global _warned_unit_weights
     if not _warned_unit_weights:
         import warnings
@@ -256,7 +260,14 @@ class HipHealpixMapper:
 
     def _load_weights(self):
         """use_pixel_weights=True, datapath=DATAPATH of heracles/healpy.py:183-189: the weight file of this resolution, if a
-        data path is configured and holds one."""
+        data path is configured and holds one.  ``pixel_weights="compute"``: the weights of (nside, lmax) computed on the GPU
+        (``compute_pixel_weights``), on first use; they replace the string and are kept."""
+        if isinstance(self.pixel_weights, str):
+            if self.pixel_weights != "compute":
+                raise ValueError(f"pixel_weights={self.pixel_weights!r}: an array of 12 nside^2 weights, None or \"compute\"")
+            from .weights import compute_pixel_weights
+
+            self.pixel_weights = compute_pixel_weights(self.__nside, self.__lmax, device="cuda")
         if self.pixel_weights is None and self.ring_weights is None:
             path = self.datapath if self.datapath is not None else type(self).DATAPATH
             if path is not None:

@@ -499,6 +499,19 @@ void hx_catmap_destroy_sel(hx_catmap_sel *ctx);
  * takes as `pix_weights`.  compressed / weights host or device.                                                           */
 int64_t hx_pixel_weights_size(int nside);
 int hx_pixel_weights_expand(int nside, int64_t ncompressed, const double *compressed, double *weights);
+/* The compressed weights themselves, computed in HBM: the minimum-norm x with map2alm_{unit weights, band limit 2 lmax}(1 + E x) =
+ * sqrt(4 pi) e_00 (E: the expansion above without the `1 +`), i.e. the weights with which map2alm(alm2map(a), niter = 0) = a for a
+ * band limit lmax.  Conjugate gradients on the normal equations from x = 0, restricted to the modes the symmetries of the
+ * pixelisation leave (real parts, L even, M = 0 mod 4); the host reads one scalar per iteration.  Bit-identical from run to run.
+ * plan    : the HEALPix plan of (nside, 2 lmax) -- anything else is HX_ERR_ARG
+ * lmax    : band limit of the transforms the weights are for, <= 3 nside / 2 (beyond that the weights make the quadrature worse:
+ *           HX_ERR_ARG)
+ * epsilon : stop when |gradient| <= epsilon |gradient at x = 0|; itmax: or after this many iterations (not an error)
+ * compressed_out : hx_pixel_weights_size(nside) doubles, host or device
+ * iterations, rel_gradient, max_residual : NULL, or the iterations used, |gradient| / |gradient at x = 0| reached, and the largest
+ *           |sqrt(4 pi) e_00 - map2alm(1 + E x)| over the constrained modes, formed anew from the x handed out             */
+int hx_pixel_weights_solve(hx_plan *plan, int lmax, double epsilon, int itmax, double *compressed_out, int *iterations,
+                           double *rel_gradient, double *max_residual);
 
 /* ---- covariance estimators of DICES (heracles/dices/jackknife.py:449-593, heracles/dices/shrinkage.py:66-98) ---------------------
  * Samples are stacked one per row in data-vector order; every array is row-major, host or device.  Columns are centred in two
