@@ -68,6 +68,12 @@ struct LegParams {
     const long long *__restrict__ arow;
     long long arow0;
     int add_all;                       // k_legendre_duo: every ring group ADDS to its (zeroed) rows -- a launch that holds only some ring groups of an m (StreamSweep)
+    // k_legendre_duo: lead-in table of the task set (leadin_table), indexed like `tasks`: the chains of ring group t as they enter block
+    // tasks[t].pad, [chain][vc | vp: 256 doubles each, sc: 256 ints]; null: every ring group starts from its seeds at block 0
+    const double *__restrict__ leadin;
+    // scout launch only (k_legendre_duo<.., SCOUT>): the task list and the table, to be written
+    LegTask *tasks_out;
+    double *leadin_out;
 };
 
 // =====================================================================================
@@ -396,7 +402,19 @@ __device__ __forceinline__ void alm_rows_to_layout(const PlanDev &P, int m, bool
 }
 
 // NSUB: 32-l blocks per flush (their D tiles stay in registers; one staging round and one pair of barriers per NSUB blocks)
-template <int SPIN, int NG, int NBX, int NSUB = 1>
+// Lead-in table (A.leadin).  What a ring group does before its first matrix instruction -- seeds, recursion, set_mode, the flag exchange of
+// every flush -- depends on the plan only, not on the maps.  With a table the group takes the state of its chains at the entry of block
+// b_res = tasks[t].pad from there and starts its block loop at b_res: the first block of a flush PAIR (even) in which any of its waves
+// would issue matrix instructions, i.e. the flush at which `started` flips.  b_res = 0: seeds as ever; b_res = nblk: the group never
+// wakes and does nothing.  The FIRST ring group of an m, which stores its rows so that nothing need be zeroed before the launch,
+// writes zeros to the rows of the blocks it skips.  The table is written by THIS kernel's own code -- SCOUT: the instantiation that
+// keeps seeds, set_mode, recursion, rescaling and the coefficient path and has no operands, no matrix block and no flush; it stops
+// at b_res and stores the state it held at the entry of that pair -- so the states are bit for bit those the sweep would hold there,
+// and they depend on SPIN and the scale step only, not on NG / NBX / NSUB.  (The scout keeps no lambda tile either: nothing reads it.)
+// RESUME: the instantiation reads the table.  The spin-2 sweeps always do (a null table is a run-time branch in the prologue); the
+// spin-0 sweeps, whose lead-in hides under the other work-group's matrix work and which gain nothing from it, are built
+// without, bres a constant 0, and only a plan that asks for the spin-0 table (hx_plan_set_leadin_resume(plan, 2)) launches <0, .., true>.
+template <int SPIN, int NG, int NBX, int NSUB = 1, bool SCOUT = false, bool RESUME = SPIN == 2>
 __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const double2 *__restrict__ coefn)
 {
     using C = PipeCfg<SPIN>;
@@ -415,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
     constexpr int TW = NSUB * DSZ > 2048 ? NSUB * DSZ : 2048;
     static_assert(NG >= 1 && NG <= 2 && TW * NW * 8 <= 81920, "two work-groups per CU");
     static_assert(SPIN == 0 || HALF_F, "spin 2: the lambda- chain carries (-1)^(l + m) lambda- (one operand row, wave-uniform coefficients)");
-    __shared__ double tile[NW][TW];            // 64 KiB (80 at most); doubles as the D staging area of the flush
+    __shared__ double tile[NW][SCOUT ? 2 : TW];  // 64 KiB (80 at most); doubles as the D staging area of the flush
     __shared__ int lead_in[2][NW];             // while no wave of the ring group has issued a matrix instruction yet: did wave w, in flush (slot) b?
     const PlanDev &P = A.P;
     const int m = A.m0 + blockIdx.x * A.ms, lmax = P.lmax;
@@ -443,14 +461,28 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
     };
     int n_mf = 0, n_rec = 0;
     if (DUO_PRIO) __builtin_amdgcn_s_setprio(3);
-    for (int ti = 0; ti < mt.count; ++ti) {
-        const LegTask task = A.tasks[mt.first + ti];
+    // (SCOUT: the ring groups of an m are independent of each other and dealt to the gridDim.y work-groups of the m)
+    const int ti0 = SCOUT ? (int)blockIdx.y : 0, tis = SCOUT ? (int)gridDim.y : 1;
+    for (int ti = ti0; ti < mt.count; ti += tis) {
+        const LegTask task = SCOUT ? A.tasks_out[mt.first + ti] : A.tasks[mt.first + ti];
         first_group = ti == 0 && !A.add_all;
+        const int bres = (RESUME && !SCOUT && A.leadin) ? task.pad : 0;  // wave-uniform
         int tid = threadIdx.x;
         asm volatile("; ring group" : "+v"(tid));
         const int w = tid >> 6, lane = tid & 63;
         const int ai = lane & 15, ak = lane >> 4;
-        if (ti) __syncthreads();  // the previous ring group's last readers of the tiles
+        if (ti != ti0) __syncthreads();  // the previous ring group's last readers of the tiles
+        if (!SCOUT && bres > 0) {
+            if (first_group) {
+                // rows of the blocks this group skips: whole rows, padding columns included (full lines).  The ring groups behind it
+                // add to some of them from OTHER waves: the stores are complete before the barrier in front of the next group
+                double2 *z = reinterpret_cast<double2 *>(A.partial + orow * A.pcol);
+                const long long nz = (long long)bres * LBLK * A.pcol / 2;
+                for (long long i = tid; i < nz; i += 256) z[i] = make_double2(0.0, 0.0);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            if (bres >= nblk) continue;  // never wakes
+        }
 
         // ring of this lane: wave w holds ring block w (spin 2) / blocks 2 w, 2 w + 1 (spin 0) of the task
         const int rbi = SPIN == 0 ? 2 * w + (lane >> 5) : w;
@@ -466,7 +498,7 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
         for (int sp = 0; sp < NPAIR; ++sp) {
             const int op = SPIN == 0 ? 0 : sp & 1, q = SPIN == 0 ? sp : sp >> 1;
             const int rbq = SPIN == 0 ? 2 * w + (q >> 3) : w;
-            const bool on = rbq < task.nrb;
+            const bool on = !SCOUT && rbq < task.nrb;
             const long long row = (long long)blockIdx.x * P.nrp_pad + (task.rb0 + rbq) * RBLK + pipe_rho(q & 7, ak);
             if (HALFB) {
                 const double *f = A.F + (row * NOP + op) * A.ncol;  // the even-parity row, for both positions
@@ -491,7 +523,15 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
         int sc[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) { vc[c] = 0.0; vp[c] = 0.0; sc[c] = -100; }
-        if (valid) {
+        if (bres > 0) {
+            const double *st = A.leadin + (long long)(mt.first + ti) * (NCH * 640) + tid;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                vc[c] = st[c * 640];
+                vp[c] = st[c * 640 + 256];
+                sc[c] = reinterpret_cast<const int *>(st + c * 640 + 512 - tid)[tid];
+            }
+        } else if (valid) {
             if (SPIN == 0) {
                 SVal a = spow(P.sth[rpl], m);
                 a.v *= P.mfac[m];
@@ -550,7 +590,7 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
                     }
                     cur[k] = rec_step(RMM, SPIN == 0 ? ((kk & 1) ? NCH - 1 : 0) : 0, SPIN == 0 ? kk >> 1 : kk, tq);
                 }
-                if (RM >= 2) {
+                if (RM >= 2 && !SCOUT) {
 #pragma unroll
                     for (int j = 0; j < HB / 2; ++j)
                         *reinterpret_cast<double2 *>(tw + pipe_tile_idx(lane, h * (HB / 2) + j)) = make_double2(cur[2 * j], cur[2 * j + 1]);
@@ -591,19 +631,26 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
         const int fcol = tid & 15, fch = (tid >> 4) & 7, fpos = (tid >> 7) & 1;
         const int frow = (fch >> 1) + 8 * (fch & 1);
         const int qrow = tid / (4 * NXA), qcol = tid % (4 * NXA);
-        double *pgrp = A.partial + (orow + 2 * frow + fpos) * A.pcol + fcol;
-        double *pquad = A.partial + (orow + 2 * qrow) * A.pcol + NG * NCOL + qcol;
-        double2 cnext[2] = {cfm[0], cfm[16]};
+        double *pgrp = A.partial + (orow + (long long)bres * LBLK + 2 * frow + fpos) * A.pcol + fcol;
+        double *pquad = A.partial + (orow + (long long)bres * LBLK + 2 * qrow) * A.pcol + NG * NCOL + qcol;
+        double2 cnext[2] = {cfm[bres * LBLK], cfm[bres * LBLK + 16]};
         // Lead-in of a ring group: the blocks in which every ring of all four waves is still dead (below 2^-300: ~ 8 % of the blocks; below 2^-100, spin 2: ~ 12 %) have
         // nothing to flush.  Until the first wave issues matrix instructions the waves exchange one flag per flush through LDS (one barrier,
         // one 16-byte read) and skip staging, reduction, atomics and the second barrier; from then on no flag is read or written any more
         // (read in EVERY flush the flags cost more than they saved: 357 vs 345 ms).  The first ring group of an m writes all its rows.
         bool started = first_group;
         int nflush = 0;
-        for (int b0 = 0; b0 < nblk; b0 += NSUB) {
+        int woke = nblk;       // SCOUT: b_res of this ring group
+        double svc[NCH], svp[NCH];
+        int ssc[NCH];
+        for (int b0 = bres; b0 < nblk; b0 += NSUB) {
             double4_t acc[NSUB][NG][2];
             double accx[NSUB][NXA][2];
             bool mine = false;
+            if (SCOUT) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) { svc[c] = vc[c]; svp[c] = vp[c]; ssc[c] = sc[c]; }
+            }
 #pragma unroll
             for (int sub = 0; sub < NSUB; ++sub) {
                 const int b = b0 + sub;
@@ -629,7 +676,7 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
                 cnext[1] = cfm[(b + 1) * LBLK + 16];
                 n_rec = __builtin_amdgcn_readfirstlane(n_rec + 1);
                 mine = mine || rm >= 2;
-                if (rm >= 2) {
+                if (!SCOUT && rm >= 2) {
                     n_mf = __builtin_amdgcn_readfirstlane(n_mf + 1);
                     if (DUO_PRIO) __builtin_amdgcn_s_setprio(0);
                     constexpr int PF = 3;
@@ -702,6 +749,17 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
             // (g 2 + p) 256 + col 16 + (c ^ (col & 7)) 2;  4-column blocks: lane (i = lane >> 4, blk = (lane >> 2) & 3, j = lane & 3) = row 4 blk + i,
             // column j, both positions in one 16-byte store at DQ0 + ((row 4 NBX + 4 x + j) 2); sub-block sub at + sub DSZ
             const bool two = NSUB > 1 && b0 + 1 < nblk;
+            if (SCOUT) {  // the flag exchange of the lead-in, and nothing else: the pair in which a wave wakes is b_res
+                if (lane == 0) lead_in[nflush & 1][w] = mine ? 1 : 0;
+                lds_barrier();
+                const int4 fl = *reinterpret_cast<const int4 *>(&lead_in[nflush & 1][0]);
+                ++nflush;
+                if (__builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w) != 0) {
+                    woke = b0;
+                    break;
+                }
+                continue;
+            }
             if (!started) {
                 if (lane == 0) lead_in[nflush & 1][w] = mine ? 1 : 0;
                 lds_barrier();
@@ -754,8 +812,20 @@ __global__ __launch_bounds__(256, 2) void k_legendre_duo(LegParams A, const doub
             pquad += (long long)NSUB * LBLK * A.pcol;
             lds_barrier();  // D tiles consumed: the tiles may be overwritten by the next block's recursion
         }
+        if (SCOUT) {
+            if (woke > 0 && woke < nblk) {
+                double *st = A.leadin_out + (long long)(mt.first + ti) * (NCH * 640) + tid;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    st[c * 640] = svc[c];
+                    st[c * 640 + 256] = svp[c];
+                    reinterpret_cast<int *>(st + c * 640 + 512 - tid)[tid] = ssc[c];
+                }
+            }
+            if (tid == 0) A.tasks_out[mt.first + ti].pad = woke;
+        }
     }  // ring groups of this m
-    if ((threadIdx.x & 63) == 0) {
+    if (!SCOUT && (threadIdx.x & 63) == 0) {
         atomicAdd(&g_exec_flops[0], (unsigned long long)n_mf * (32ull * (NG * 2048ull + NBX * 512ull)));
         atomicAdd(&g_exec_flops[1], (unsigned long long)n_rec * (64ull * LBLK * 4ull));
     }
@@ -924,6 +994,13 @@ static int launch_duo(const SweepShape &sh, dim3 pgrid, hipStream_t st, const Le
     // two l-blocks per flush wherever the second accumulator set fits the 256 registers (ten spin-0 maps 105 -> 101 ms, five spin-2 fields
     // 206 -> 198, eight 289 -> 276, nine 320 -> 304; sixteen spin-0 maps spill: 147 -> 157; ten fields spill 43 registers: 345 -> 423);
     // one block per flush for the shapes named there (bit-identical results either way)
+    if (SPIN == 0 && A.leadin) {  // the spin-0 table, on request only (leadin_table)
+        if (key == 10) hipLaunchKernelGGL((k_legendre_duo<0, 1, 0, 2, false, true>), pgrid, db, 0, st, A, cn);
+        else if (key == 11) hipLaunchKernelGGL((k_legendre_duo<0, 1, 1, 2, false, true>), pgrid, db, 0, st, A, cn);
+        else if (key == 20) hipLaunchKernelGGL((k_legendre_duo<0, 2, 0, 1, false, true>), pgrid, db, 0, st, A, cn);
+        else return fail(HX_ERR_ARG, "legendre analysis: no two-group kernel for %d groups + %d blocks", sh.ng, sh.nbx);
+        return HX_OK;
+    }
     if (key == 10) hipLaunchKernelGGL((k_legendre_duo<SPIN, 1, 0, 2>), pgrid, db, 0, st, A, cn);
     else if (key == 11) hipLaunchKernelGGL((k_legendre_duo<SPIN, 1, 1, 2>), pgrid, db, 0, st, A, cn);
     else if (key == 20 && SPIN == 2) hipLaunchKernelGGL((k_legendre_duo<2, 2, 0, 2>), pgrid, db, 0, st, A, cn);
@@ -932,6 +1009,52 @@ static int launch_duo(const SweepShape &sh, dim3 pgrid, hipStream_t st, const Le
     else if (key == 20) hipLaunchKernelGGL((k_legendre_duo<SPIN, 2, 0>), pgrid, db, 0, st, A, cn);
     else if (key == 22 && SPIN == 2) hipLaunchKernelGGL((k_legendre_duo<2, 2, 2>), pgrid, db, 0, st, A, cn);
     else return fail(HX_ERR_ARG, "legendre analysis: no two-group kernel for %d groups + %d blocks", sh.ng, sh.nbx);
+    return HX_OK;
+}
+
+// The lead-in table of a task set of k_legendre_duo (see the kernel), built on the library stream by the scout instantiation when a sweep
+// first asks for it: 5 KiB (spin 2) / 10 KiB (spin 0) per ring group, 1.3 GB per spin at nside 4096 / lmax 6144.  It is scratch
+// (counted by hx_plan_scratch_bytes, freed by hx_plan_release_scratch, rebuilt on the next use) and it is capped: a table of more
+// than LEADIN_CAP_BYTES (hx_plan_set_leadin_cap), or of more than a tenth of the free device memory, is not built and the sweeps of
+// that task set run from their seeds.  *tab = null then, and where the plan's switch (hx_plan_set_leadin_resume) does not ask for
+// it: 0 = no table, 1 (default) = the spin-2 table, 2 = the spin-0 table as well.  Callers build it AFTER the scratch of their sweeps
+// (F, rows, Y, staging), which was budgeted without it: a table that no longer fits falls back, a sweep's scratch must not.
+constexpr long long LEADIN_CAP_BYTES = 8LL << 30;
+static int leadin_table(hx_plan *pl, int spin, hx_plan::SpinData &sd, hx_plan::TaskSet &ts, const double **tab)
+{
+    *tab = nullptr;
+    if (pl->leadin_resume < (spin == 0 ? 2 : 1) || ts.tasks.empty() || ts.leadin_skip) return HX_OK;
+    if (ts.d_leadin.p) {
+        *tab = ts.d_leadin.as<double>();
+        return HX_OK;
+    }
+    const size_t per_task = (size_t)(spin == 0 ? PipeCfg<0>::NCH : PipeCfg<2>::NCH) * 640 * sizeof(double);
+    const size_t bytes = ts.tasks.size() * per_task;
+    size_t cap = (size_t)(pl->leadin_cap > 0 ? pl->leadin_cap : LEADIN_CAP_BYTES), fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap = std::min(cap, fr / 10);
+    else (void)hipGetLastError();
+    if (bytes > cap) {
+        ts.leadin_skip = true;
+        return HX_OK;
+    }
+    if (ts.d_leadin.alloc(bytes) != HX_OK) {  // (no room after all: the same fallback)
+        (void)hipGetLastError();
+        ts.leadin_skip = true;
+        return HX_OK;
+    }
+    LegParams A;
+    A.P = pl->dev(); A.tasks = nullptr; A.F = nullptr; A.partial = nullptr;
+    A.m0 = 0; A.ms = 1; A.row0 = 0; A.ng = 1; A.ncol = NCOL; A.pcol = NCOL;
+    A.of_m = ts.d_of_m.as<MTasks>(); A.arow = ts.d_arow.as<long long>(); A.arow0 = 0; A.add_all = 1;
+    A.leadin = nullptr; A.tasks_out = ts.d_tasks.as<LegTask>(); A.leadin_out = ts.d_leadin.as<double>();
+    const dim3 grid((unsigned)(pl->lmax + 1), 8), db(256);  // (without matrix work a ring group is one latency-bound chain: eight work-groups per m)
+    if (spin == 0) hipLaunchKernelGGL((k_legendre_duo<0, 1, 0, 2, true>), grid, db, 0, rt().stream, A, sd.cn.as<double2>());
+    else hipLaunchKernelGGL((k_legendre_duo<2, 1, 0, 2, true>), grid, db, 0, rt().stream, A, sd.cn.as<double2>());
+    if (hipGetLastError() != hipSuccess) {  // (d_leadin.p doubles as "the table is built": nothing half-made stays behind)
+        ts.d_leadin.release();
+        return fail(HX_ERR_HIP, "leadin_table: the scout launch failed");
+    }
+    *tab = ts.d_leadin.as<double>();
     return HX_OK;
 }
 
@@ -952,7 +1075,7 @@ static void launch_alm_reduce(hx_plan *pl, int spin, hx_plan::TaskSet &ts, long 
 
 template <int SPIN>
 static int launch_chunk(hx_plan *pl, hx_plan::SpinData &sd, hx_plan::TaskSet &ts, int m0, int m1, int nb, const SweepShape &sh, const double *d_rw,
-                        const double *d_fl, int add, double2 *d_alms)
+                        const double *d_fl, int add, double2 *d_alms, const double *leadin)
 {
     // column groups of the F / partial rows: full groups (+ 1 holding the extra blocks)
     const int ng = sh.ng + (sh.nbx > 0 ? 1 : 0), ncol = sh.ncol;
@@ -975,6 +1098,7 @@ static int launch_chunk(hx_plan *pl, hx_plan::SpinData &sd, hx_plan::TaskSet &ts
         A.m0 = m0; A.ms = ms; A.row0 = ts.rows_before_m[m0]; A.ng = ng; A.ncol = ncol; A.pcol = pcol;
         A.of_m = ts.d_of_m.as<MTasks>(); A.arow = ts.d_arow.as<long long>(); A.arow0 = ts.arow[m0]; A.add_all = 0;
         A.tasks = ts.d_tasks.as<LegTask>();  // (the kernel indexes the whole list through of_m)
+        A.leadin = leadin; A.tasks_out = nullptr; A.leadin_out = nullptr;
         // (no memset of the rows: the first ring group of an m stores them)
         HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, sd.cn.as<double2>()));
     }
@@ -1090,11 +1214,13 @@ int analysis_batch(hx_plan *pl, int spin, int nb, const double *d_maps, double2 
     // rows of the partial buffer: one span per m (the pipelined kernel adds its ring groups in place), sweep_pcol doubles each
     std::vector<std::pair<int, int>> chunks;
     HX_TRY(plan_m_chunks(pl, (double)pl->nrp_pad * analysis_f_rows(spin) * sh.ncol * sizeof(double), ts->arow, sweep_pcol(sh) * sizeof(double), chunks));
+    const double *leadin = nullptr;
+    HX_TRY(leadin_table(pl, spin, *sd, *ts, &leadin));
     for (auto &ch : chunks) {
         if (spin == 0)
-            HX_TRY(launch_chunk<0>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
+            HX_TRY(launch_chunk<0>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms, leadin));
         else
-            HX_TRY(launch_chunk<2>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms));
+            HX_TRY(launch_chunk<2>(pl, *sd, *ts, ch.first, ch.second, nb, sh, d_rw, d_fl, add, d_alms, leadin));
     }
     return HX_OK;
 }
@@ -1138,6 +1264,7 @@ int analysis_stream_plan(hx_plan *pl, int spin, int nb, int nslab, StreamSweep &
     HX_TRY(task_set(pl, spin, false, one_set_task_blocks(spin), &s.ts));
     hx_plan::TaskSet &ts = *s.ts;
     const SweepShape sh = sweep_shape(spin, nb);
+    s.leadin = nullptr;
     s.pl = pl; s.spin = spin; s.nb = nb;
     // slab edges: whole 32-ring-pair blocks, about equal numbers of pixels (a ring pair is 8 nsub pixels, the equator ring 4)
     const int nrb = (pl->nrp + RBLK - 1) / RBLK;
@@ -1179,6 +1306,9 @@ int analysis_stream_plan(hx_plan *pl, int spin, int nb, int nslab, StreamSweep &
     return HX_OK;
 }
 
+// the lead-in table of a planned sweep: once the scratch of ALL sweeps of the call stands (see leadin_table)
+int analysis_stream_leadin(StreamSweep &s) { return leadin_table(s.pl, s.spin, *s.sd, *s.ts, &s.leadin); }
+
 int analysis_stream_start(StreamSweep &s)
 {
     hx_plan *pl = s.pl;
@@ -1213,6 +1343,7 @@ static int stream_slab(StreamSweep &s, int k)
         A.P = P; A.tasks = ts.d_tasks.as<LegTask>(); A.F = pl->F.as<double>(); A.partial = pl->partial.as<double>();
         A.m0 = 0; A.ms = 1; A.row0 = 0; A.ng = ng; A.ncol = sh.ncol; A.pcol = sweep_pcol(sh);
         A.of_m = s.d_of_m.as<MTasks>() + (size_t)k * (lmax + 1); A.arow = ts.d_arow.as<long long>(); A.arow0 = 0; A.add_all = 1;
+        A.leadin = s.leadin; A.tasks_out = nullptr; A.leadin_out = nullptr;
         HX_TRY(launch_duo<SPIN>(sh, dim3((unsigned)nm), st, A, s.sd->cn.as<double2>()));
     }
     HX_HIP(hipGetLastError());

@@ -133,6 +133,8 @@ static int map2alm_multi_impl(hx_plan *pl, int njobs, const int *spins, const in
         ss[k].d_alms = valm[w.job].as<double2>() + (size_t)w.c0 * pl->nlm;
         ss[k].d_rw = vrw.as<double>(); ss[k].d_pw = vpw.as<double>(); ss[k].d_fl = vfl[w.job].as<double>();
     }
+    for (size_t k = 0; k < sweeps.size(); ++k)
+        if (sweeps[k].stream) HX_TRY(analysis_stream_leadin(ss[k]));
     // units of work in order: a whole sweep, or one slab of a streamed sweep; units of host sweeps have an upload in front of them
     struct Unit { size_t k; int slab; };
     std::vector<Unit> units;

@@ -265,6 +265,27 @@ extern "C" int hx_plan_release_scratch(hx_plan *pl)
     pl->F.release();
     pl->partial.release();
     pl->syn_tab.release();
+    for (auto &sp : pl->spins)
+        for (auto &kv : sp.second.tasks) {  // lead-in tables: rebuilt by the next sweep that wants one
+            kv.second.d_leadin.release();
+            kv.second.leadin_skip = false;
+        }
+    return HX_OK;
+}
+
+extern "C" int hx_plan_set_leadin_resume(hx_plan *pl, int on)
+{
+    if (!pl) return fail(HX_ERR_ARG, "hx_plan_set_leadin_resume: null plan");
+    pl->leadin_resume = on < 0 ? 0 : (on > 2 ? 2 : on);
+    return HX_OK;
+}
+
+extern "C" int hx_plan_set_leadin_cap(hx_plan *pl, int64_t bytes)
+{
+    if (!pl || bytes < 0) return fail(HX_ERR_ARG, "hx_plan_set_leadin_cap: null plan or negative cap");
+    pl->leadin_cap = bytes;
+    for (auto &sp : pl->spins)
+        for (auto &kv : sp.second.tasks) kv.second.leadin_skip = false;  // (asked again under the new cap)
     return HX_OK;
 }
 
@@ -272,7 +293,10 @@ extern "C" int64_t hx_plan_scratch_bytes(const hx_plan *pl)
 {
     if (!pl) return 0;
     size_t spin_tables = 0;
-    for (const auto &kv : pl->spins) spin_tables += kv.second.cn.bytes + kv.second.al.bytes;
+    for (const auto &kv : pl->spins) {
+        spin_tables += kv.second.cn.bytes + kv.second.al.bytes;
+        for (const auto &ts : kv.second.tasks) spin_tables += ts.second.d_leadin.bytes;
+    }
     return (int64_t)(pl->stage[0].bytes + pl->stage[1].bytes + pl->stage[2].bytes + pl->resid_maps.bytes + pl->Y.bytes + pl->F.bytes + pl->partial.bytes +
                      pl->bhat.bytes + pl->syn_tab.bytes + spin_tables);
 }

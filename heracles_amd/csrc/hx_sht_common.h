@@ -366,6 +366,8 @@ struct hx_plan {
     // orders the analysis sweeps cover: m_lo, m_lo + m_step, ... < m_hi (m_hi < 0 = lmax + 1).  The m-sharded route gives rank q of N
     // the orders q, q + N, ...: every rank gets every size of work-group, and as many of them as a single GPU's launch / N
     int m_lo = 0, m_hi = -1, m_step = 1;
+    int leadin_resume = 1;        // k_legendre_duo resumes its ring groups from the lead-in table: 0 no, 1 spin 2, 2 spin 0 as well (hx_plan_set_leadin_resume)
+    long long leadin_cap = 0;     // cap of one task set's table in bytes; 0: LEADIN_CAP_BYTES (hx_plan_set_leadin_cap)
     long long npix = 0, ny = 0, nlm = 0;
     size_t lds_fft = 0;
     hx::DevBuf z, omz, sth, rwdef, nsub, shifted, startN, startS, bhat_off, tw, bhat, mfac, kfac2;
@@ -379,6 +381,10 @@ struct hx_plan {
         std::vector<long long> rows_before_m; // partial rows of all tasks with smaller m (size lmax+2)
         std::vector<long long> arow;          // the same with ONE span of rows per m (pipelined kernel: ring groups summed in place)
         hx::DevBuf d_tasks, d_of_m, d_arow;
+        // lead-in table of k_legendre_duo (leadin_table, hx_analysis.hip): chain states at the resume block of every task; the resume
+        // blocks themselves sit in LegTask::pad of d_tasks.  Rebuildable: scratch (hx_plan_release_scratch frees it)
+        hx::DevBuf d_leadin;
+        bool leadin_skip = false;             // the table went over its cap when it was last asked for: today's path until the scratch is released
     };
     // What the Legendre sweeps of one spin weight need of a plan, per kernel family: the kernels specialised for spin 0 / spin 2 (their
     // seed factors are mfac / kfac2 above; tables of k_init_norm0 / k_init_norm2) and the run-time-spin sweeps of the vector unit (any
@@ -449,8 +455,10 @@ struct StreamSweep {
     DevBuf d_of_m;              // [nslab][lmax + 1]: the ring groups of order m that are complete with slab k
     hx_plan::SpinData *sd = nullptr;  // tables and tasks (one ring set per wave) the sweep runs with
     hx_plan::TaskSet *ts = nullptr;
+    const double *leadin = nullptr;   // lead-in table of ts for this sweep, or null (leadin_table, hx_analysis.hip)
 };
 bool analysis_can_stream(hx_plan *pl, int spin, int nb);
+int analysis_stream_leadin(StreamSweep &s);  // after analysis_stream_plan of every sweep of the call: the lead-in table, if the plan wants one and it still fits
 int analysis_stream_plan(hx_plan *pl, int spin, int nb, int nslab, StreamSweep &s);   // slab edges, task tables, scratch (grown, never shrunk): before anything of the call is queued
 int analysis_stream_start(StreamSweep &s);  // zeroes the accumulation rows (queued on the library stream, in front of slab 0)
 int analysis_stream_slab(StreamSweep &s, int k);

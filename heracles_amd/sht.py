@@ -49,6 +49,14 @@ class Plan:
         except Exception:  # noqa: BLE001
             pass
 
+    def set_leadin_resume(self, on: bool = True, cap_bytes: int | None = None, spin0: bool = False):
+        """Switch of the lead-in table of the batched Legendre analysis (hx_plan_set_leadin_resume; default on for the spin-2 sweeps,
+        `spin0` asks for the table of the spin-0 sweeps as well; alms bit-identical either way) and, if given, the cap of one table
+        in bytes (hx_plan_set_leadin_cap; 0 = the default of 8 GiB; holds for tables built from now on)."""
+        _lib.check(_lib.load().hx_plan_set_leadin_resume(self._h, (2 if spin0 else 1) if on else 0))
+        if cap_bytes is not None:
+            _lib.check(_lib.load().hx_plan_set_leadin_cap(self._h, int(cap_bytes)))
+
     @property
     def scratch_bytes(self) -> int:
         return int(_lib.load().hx_plan_scratch_bytes(self._h))

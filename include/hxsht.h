@@ -80,6 +80,17 @@ int64_t hx_plan_scratch_bytes(const hx_plan *plan);
 /* Frees the plan's transient HBM scratch (ring spectra, Legendre operands and rows, staging buffers of host maps, residual maps,
  * synthesis tables: up to ~200 GB after a full-size job).  Everything is allocated again on demand; the tables of the plan stay. */
 int hx_plan_release_scratch(hx_plan *plan);
+/* Lead-in table of the batched Legendre analysis (5 or more spin-0 maps / 3 or more spin-2 fields per sweep).  What a ring group
+ * computes before its first matrix instruction depends on the plan only, so its chain states at that point are kept in HBM (built by
+ * the kernel's own code on the first such sweep; 1.3 GB per spin at nside 4096 / lmax 6144; counted by hx_plan_scratch_bytes, freed
+ * by hx_plan_release_scratch and rebuilt on the next use) and every later sweep resumes from them.  The alms are bit-identical with
+ * and without.  on = 0 runs every ring group from its seeds; on = 1 (default) keeps the table of the spin-2 sweeps, which it makes
+ * faster; on = 2 keeps one for the spin-0 sweeps as well (as much memory again, fewer vector instructions, no gain in time: their
+ * lead-in hides under matrix work).  The table of a task set is not built -- and its sweeps run from the seeds -- if it would exceed
+ * the cap (bytes; 0 = the default of 8 GiB) or a tenth of the device memory that is free once the sweep's scratch stands.  The cap
+ * is applied when a table is built: lowering it does not drop a larger table that exists (hx_plan_release_scratch does). */
+int hx_plan_set_leadin_resume(hx_plan *plan, int on);
+int hx_plan_set_leadin_cap(hx_plan *plan, int64_t bytes);
 /* HBM the analysis may use for the operands and ring-group partial sums of ONE m-chunk (bytes; a chunk always
  * holds at least one m).  0 (default) = min(80 GB, half of the free HBM); the environment variable
  * HX_SCRATCH_GB sets the initial value.  The result does not depend on the chunking (tests/test_gpu_sht.py). */
