@@ -11,7 +11,9 @@
 // ang2pix follows the published HEALPix algorithm (Gorski et al. 2005; healpix_cxx
 // T_Healpix_Base::loc2pix, RING branch), the third-party code healpy calls; it is absent
 // from /root/reference, so index parity is pinned on the test-side numpy restatement
-// and on the pix2ang round trip of every pixel centre (tests/test_gpu_mapper.py).
+// and on the pix2ang round trip of every pixel centre (tests/test_gpu_mapper.py), and at
+// pixel edges on the exact pixel and admissible set of tests/pixel_reference.py
+// (tests/test_gpu_pixel_edges.py).
 #include "hx_common.h"
 
 #include "hx_sort.h"
@@ -44,7 +46,10 @@ __device__ inline long long ang2pix_ring_one(long long nside, double lon_deg, do
     double phi = lon_deg * kDeg2Rad;
     double z = cos(theta);
     bool have_sth = (theta < 0.01) || (theta > 3.14159 - 0.01);
-    double sth = have_sth ? sin(theta) : 0.0;
+    // theta in (pi, pi + 1e-5] passes lonlat_valid as it passes healpy's check; its sine is negative, and from nside 2^17 on a negative
+    // tmp truncates to negative jp, jm and a pixel hundreds of rings from the pole.  Clamped, such a point falls in the last ring
+    // (ir = 1), where the truncation towards zero already put it at every smaller nside.  sin >= 0 for every double theta in [0, pi].
+    double sth = have_sth ? fmax(sin(theta), 0.0) : 0.0;
     double za = fabs(z);
     double tt = fmodulo4(phi * kInvHalfPi);
     long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1), nl4 = 4 * nside;
@@ -73,7 +78,9 @@ __device__ inline long long ang2pix_ring_one(long long nside, double lon_deg, do
 // healpy.ang2pix validates its input (check_theta_valid: 0 <= theta <= pi + 1e-5, which a NaN fails) and
 // raises ValueError before any pixel is touched; the formulas above yield negative or out-of-range
 // indices for such points.  Invalid points (a non-finite longitude included) get pixel -1 and are counted
-// in *nbad; the entry points return HX_ERR_ARG before anything is scattered.
+// in *nbad; the entry points return HX_ERR_ARG before anything is scattered.  The rule is evaluated on the
+// double theta = pi/2 - radians(lat): a latitude an ulp beyond +-90 whose theta rounds to 0 or pi is accepted,
+// and an accepted theta in (pi, pi + 1e-5] gets a pixel of the last ring (tests/test_gpu_pixel_edges.py).
 __device__ inline bool lonlat_valid(double lon_deg, double lat_deg)
 {
 #pragma clang fp contract(off)
@@ -206,6 +213,8 @@ __device__ inline long long ring2nest_dev(int order, long long pring)
 
 // numpy's pairwise summation (the arithmetic behind healpy's np.sum(axis=1) in _ud_grade_core):
 // n < 8 sequential from 0; n <= 128 eight strided accumulators; else split at n/2 rounded to 8.
+// numpy hands a reduction to this routine in pieces of its ufunc buffer (8192 elements) and adds the
+// pieces' sums in order: numpy_sum below.  For ud_grade the two differ from 65536 children on (nside ratio 256).
 template <class Load>
 __device__ double numpy_pairwise_sum(long long i0, long long n, Load load)
 {
@@ -229,6 +238,18 @@ __device__ double numpy_pairwise_sum(long long i0, long long n, Load load)
     long long n2 = n / 2;
     n2 -= n2 % 8;
     return numpy_pairwise_sum(i0, n2, load) + numpy_pairwise_sum(i0 + n2, n - n2, load);
+}
+
+constexpr long long kNumpyBufsize = 8192;
+
+template <class Load>
+__device__ double numpy_sum(long long n, Load load)
+{
+#pragma clang fp contract(off)
+    double res = numpy_pairwise_sum(0, n < kNumpyBufsize ? n : kNumpyBufsize, load);
+    for (long long i0 = kNumpyBufsize; i0 < n; i0 += kNumpyBufsize)
+        res += numpy_pairwise_sum(i0, (n - i0 < kNumpyBufsize) ? n - i0 : kNumpyBufsize, load);
+    return res;
 }
 
 constexpr double kUnseen = -1.6375e30;
@@ -256,7 +277,7 @@ __global__ __launch_bounds__(256) void k_ud_grade(int order_in, int order_out, c
         nhit += good;
         return good ? v : v * 0.0;
     };
-    const double s = numpy_pairwise_sum(0, rat2, load);
+    const double s = numpy_sum(rat2, load);
     dst[p] = nhit ? s / (double)nhit : kUnseen;
 }
 

@@ -86,7 +86,12 @@ def _native(arr):
 
 def ang2pix_ring(nside, lon, lat, out=None):
     """RING pixel index of (lon, lat) in degrees on the GPU: ``hp.ang2pix(nside, lon, lat,
-    lonlat=True)`` of heracles/healpy.py:157.  numpy arrays or device tensors."""
+    lonlat=True)`` of heracles/healpy.py:157.  numpy arrays or device tensors.
+
+    A point is accepted iff its longitude is finite and ``0 <= theta_d <= pi + 1e-5`` for the double
+    ``theta_d = pi/2 - radians(lat)`` (healpy's ``check_theta_valid``); one rejected point raises ``ValueError`` for the whole
+    call.  So a latitude an ulp beyond +-90 is accepted where its ``theta_d`` rounds to 0 or pi and rejected where it does not,
+    and an accepted ``theta_d`` in (pi, pi + 1e-5] gets a pixel of the last ring."""
     from . import _lib
 
     _lib.ensure_init()
