@@ -120,6 +120,7 @@ int launch_gemm_tst(const double *T, int rows1_pad, const double *T2, int rows2_
 void mixmat_drop_cache();
 void alm2cl_drop_cache();  // hx_twopoint.hip: the buffers hx_alm2cl_pairs keeps between calls
 void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner tables hx_cl2corr / hx_corr2cl keep for the last lmax
+void synalm_drop_cache();  // hx_synalm.hip: the factor hx_synalm / hx_cl_cholesky keep between calls
 
 int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  // hx_transforms.hip: those tables, for hx_xi_cols.hip
 // Gauss-Legendre nodes/weights into device arrays (hx_mixmat.hip)

@@ -1183,6 +1183,7 @@ extern "C" int hx_release_caches(void)
     mix_cache_drop();
     alm2cl_drop_cache();
     corr_cache_drop();
+    synalm_drop_cache();
     return HX_OK;
 }
 

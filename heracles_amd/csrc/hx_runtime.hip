@@ -475,6 +475,7 @@ int hx_init(int device)
         r.order_ev = nullptr;
         mixmat_drop_cache();
         alm2cl_drop_cache();
+        synalm_drop_cache();
         stager_reset_events();
     }
     HX_HIP(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));

@@ -541,6 +541,19 @@ int hx_cov_delete2(int njk, int m, int N, const double *c0, const double *c1, co
                    int nb, const int *bstart, double alpha, double *out);
 int hx_cov_shrink_sums(int n, int N, const double *x, const double *target, int64_t ldt, double *out);
 
+/* ---- Gaussian mock alms of a set of spectra ------------------------------------------------------------------------
+ * cl   : (ncomp (ncomp + 1) / 2, lmax + 1), the symmetric matrix of spectra C^{ij}_l, rows in the order of
+ *        itertools.combinations_with_replacement(range(ncomp), 2) -- the array hx_alm2cl_pairs returns for that pair list
+ * alms : (ncomp, nlm) complex128, a^i_lm = sum_{j <= i} L_ij(l) z^j_lm: L_l the lower Cholesky factor of C_l (no pivoting; a pivot
+ *        d <= 4 ncomp 2^-52 C_jj zeroes its column), z complex standard normals from Philox4x32-10 with key (seed & 0xffffffff,
+ *        seed >> 32) and counter (l, m, j, realisation): a realisation does not depend on lmax
+ * chol : the factor alone, (ncomp (ncomp + 1) / 2, lmax + 1), same packing, L_ij with i >= j at the row of pair (j, i)
+ * Host or device pointers, as everywhere in this header.  1 <= ncomp <= 64, lmax >= 0, else HX_ERR_ARG.  A matrix that is not positive
+ * semi-definite (a pivot below -4 ncomp 2^-52 C_jj), NaN or Inf: HX_ERR_ARG, hx_last_error names the smallest such l, nothing is written.
+ * The factor of the last call stays in HBM (ncomp (ncomp + 1) / 2 x (lmax + 1) doubles) until hx_release_caches. */
+int hx_synalm(int ncomp, int lmax, const double *cl, uint64_t seed, uint32_t realisation, double *alms);
+int hx_cl_cholesky(int ncomp, int lmax, const double *cl, double *chol);
+
 #ifdef __cplusplus
 }
 #endif
