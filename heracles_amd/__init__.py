@@ -41,7 +41,7 @@ from .fields import (
     get_masks,
 )
 from .mapping import catalog_alms, map_catalogs, transform
-from .mocks import gaussian_maps, synalm, synalm_components
+from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
 from .sht import Plan, get_plan
 from .transforms import cl2corr, cl2corr_columns, corr2cl, corr2cl_columns, gauss_legendre, wigner_d_table
 from .fits import read_vmap
@@ -72,5 +72,5 @@ __all__ = [
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
     "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
-    "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps",
+    "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
 ]

@@ -554,6 +554,21 @@ int hx_cov_shrink_sums(int n, int N, const double *x, const double *target, int6
 int hx_synalm(int ncomp, int lmax, const double *cl, uint64_t seed, uint32_t realisation, double *alms);
 int hx_cl_cholesky(int ncomp, int lmax, const double *cl, double *chol);
 
+/* ---- Poisson-sampled mock catalogues from expected-count maps ------------------------------------------------------
+ * Both calls work on a range [pix_begin, pix_end) of RING pixels of `nside` (1 .. 8192, any integer); every array covers that range
+ * only, so a catalogue can be made in pieces.  A realisation is a function of (seed, realisation, nside, pixel, index) alone.
+ * hx_mockcat_counts: counts[p - pix_begin] ~ Poisson(lam[p - pix_begin]) (int64), *total (host) their sum.  A lam that is NaN,
+ *   negative, infinite or above 2^30 (hx_last_error names the first such pixel), or a total >= 2^31: HX_ERR_ARG, nothing is written.
+ * hx_mockcat_points: the points of those counts, sorted by pixel, then by index within the pixel: lon / lat in degrees (lon in
+ *   [0, 360), the conventions of hx_ang2pix_ring), values [nval][total] with values[j][g] = maps[j][p - pix_begin] + sigma[j] x a
+ *   standard normal (sigma[j] == 0 adds nothing), and, unless NULL, pix[g] = the RING pixel p of point g.  maps: [nval][pix_end -
+ *   pix_begin]; total is the sum of the counts, < 2^31.  A negative count or a larger total: HX_ERR_ARG, nothing is written.
+ * Host or device pointers, as everywhere in this header. */
+int hx_mockcat_counts(int nside, int64_t pix_begin, int64_t pix_end, const double *lam, uint64_t seed, uint32_t realisation, int64_t *counts,
+                      int64_t *total);
+int hx_mockcat_points(int nside, int64_t pix_begin, int64_t pix_end, const int64_t *counts, uint64_t seed, uint32_t realisation, int nval,
+                      const double *maps, const double *sigma, double *lon, double *lat, double *values, int64_t *pix);
+
 #ifdef __cplusplus
 }
 #endif
