@@ -63,6 +63,17 @@ class RegionAlms:
         return self._dress(work)
 
 
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+def _labels_of(jk_map):
+    """``jk_map`` as given if it is a tensor (``hx.jackknife_regions`` of a CUDA map: it stays where it is), else as a numpy array."""
+    if isinstance(jk_map, DeviceArray):
+        jk_map = jk_map.tensor
+    return jk_map if _is_tensor(jk_map) else np.asarray(jk_map)
+
+
 def _mapper_of(field):
     m = getattr(field, "mapper_or_error", None)
     return m if m is not None else field.mapper
@@ -79,8 +90,11 @@ def region_alms(fields, maps, jk_map, *, device="cuda"):
     keys = list(maps)
     if not keys:
         raise ValueError("no maps")
-    jk_map = np.asarray(jk_map)
-    njk = len(np.unique(jk_map)[np.unique(jk_map) != 0])
+    jk_map = _labels_of(jk_map)
+    if _is_tensor(jk_map):
+        njk = int(torch.count_nonzero(torch.unique(jk_map) != 0))
+    else:
+        njk = len(np.unique(jk_map)[np.unique(jk_map) != 0])
     mappers = {k: _mapper_of(fields[k[0]]) for k in keys}
     m0 = mappers[keys[0]]
     if any((m.nside, m.lmax) != (m0.nside, m0.lmax) for m in mappers.values()):
@@ -102,7 +116,10 @@ def region_alms(fields, maps, jk_map, *, device="cuda"):
         meta[k] = md
     ncomp = c
     out = torch.empty((njk + 1, ncomp, nlm), dtype=torch.complex128, device=device)
-    region = torch.as_tensor(np.ascontiguousarray(jk_map, dtype=np.float64)).to(device)
+    if _is_tensor(jk_map):
+        region = jk_map.to(device=device, dtype=torch.float64).contiguous()
+    else:
+        region = torch.as_tensor(np.ascontiguousarray(jk_map, dtype=np.float64)).to(device)
     L = _lib.load()
 
     # the weight file of a configured data path is part of a mapper's settings: load it before the mappers are compared, as
@@ -164,7 +181,15 @@ def region_alms(fields, maps, jk_map, *, device="cuda"):
 def jackknife_fsky(jk_map, jk=0, jk2=0, ratio=True):
     """Sky fraction left after removing regions jk and jk2, relative to the footprint (pixels with a non-zero
     region label) if ``ratio`` (heracles/dices/jackknife.py:349-367)."""
-    jk_map = np.asarray(jk_map)
+    jk_map = _labels_of(jk_map)
+    if _is_tensor(jk_map):
+        # the same two counts, made where the labels are: only the integers reach the host
+        import torch
+
+        inside = jk_map > 0
+        size = jk_map.numel()
+        kept = int(torch.count_nonzero(inside & (jk_map != jk) & (jk_map != jk2))) / size
+        return kept / (int(torch.count_nonzero(inside)) / size) if ratio else kept
     inside = jk_map > 0
     kept = np.count_nonzero(inside & (jk_map != jk) & (jk_map != jk2)) / jk_map.size
     return kept / (np.count_nonzero(inside) / jk_map.size) if ratio else kept

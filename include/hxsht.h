@@ -569,6 +569,17 @@ int hx_mockcat_counts(int nside, int64_t pix_begin, int64_t pix_end, const doubl
 int hx_mockcat_points(int nside, int64_t pix_begin, int64_t pix_end, const int64_t *counts, uint64_t seed, uint32_t realisation, int nval,
                       const double *maps, const double *sigma, double *lon, double *lat, double *values, int64_t *pix);
 
+/* ---- jackknife regions: equal-weight segmentation of a weighted footprint -------------------------------------------
+ * No counterpart in the reference: its tutorial takes the region map from a third-party host package.  weight [12 nside^2] (RING,
+ * nside 1 .. 8192, any integer) is cut into njk (1 .. 4096) compact regions of equal summed weight by recursive weighted bisection
+ * along the principal axis: labels[p] = 0 where weight[p] <= 0, else the region 1 .. njk of pixel p.  The result is a function of
+ * (nside, weight, njk) alone and bit-identical from run to run.
+ * region_weight (NULL or [njk]): region_weight[k - 1] = the summed weight of label k.  axes (NULL or [(njk - 1) * 3]): axes[3 (b - 2) ..]
+ * is the unit axis of the split whose right part starts at label b (every b in 2 .. njk occurs once).
+ * HX_ERR_ARG, nothing written: a NaN, negative or infinite weight (hx_last_error names the first such pixel), fewer footprint pixels
+ * than njk, njk or nside out of range.  Host or device pointers, as everywhere in this header. */
+int hx_jk_regions(int nside, const double *weight, int njk, int32_t *labels, double *region_weight, double *axes);
+
 #ifdef __cplusplus
 }
 #endif
