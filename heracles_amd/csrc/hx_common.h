@@ -81,6 +81,15 @@ struct DevBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+// a host vector into a device buffer sized for it (complete on return)
+template <class T>
+int upload_vec(DevBuf &b, const std::vector<T> &v)
+{
+    HX_TRY(b.alloc(sizeof(T) * (v.empty() ? 1 : v.size())));
+    if (!v.empty()) HX_HIP(hipMemcpy(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return HX_OK;
+}
+
 // Input view: device pointer as-is, host pointer copied to a temporary device buffer.
 struct InView {
     const void *dev = nullptr;
@@ -113,9 +122,6 @@ int finish_call();  // synchronise unless async
 // Scratch budget of one analysis m-chunk in bytes (hx_set_scratch_budget, else HX_SCRATCH_GB); 0 = automatic
 double scratch_budget_bytes();
 
-// G = T diag(s) T2^T on the FP64 matrix unit (hx_mixmat.hip; used by hx_svd.hip)
-int launch_gemm_tst(const double *T, int rows1_pad, const double *T2, int rows2_pad, int kpad, const double *s, int n1, int n2, double *G, long long ldg);
-
 // hx_init on another device: drop the context hx_mixmat / hx_mixmat_eb keep between calls (hx_mixmat.hip)
 void mixmat_drop_cache();
 void alm2cl_drop_cache();  // hx_twopoint.hip: the buffers hx_alm2cl_pairs keeps between calls
@@ -123,18 +129,8 @@ void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner table
 void synalm_drop_cache();  // hx_synalm.hip: the factor hx_synalm / hx_cl_cholesky keep between calls
 
 int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  // hx_transforms.hip: those tables, for hx_xi_cols.hip
-// Gauss-Legendre nodes/weights into device arrays (hx_mixmat.hip)
-int launch_gauss_legendre(int n, double *d_x, double *d_w, double *d_xlo = nullptr);  // d_xlo: node k = x[k] + xlo[k] (see k_gauss_legendre)
-
-// Wigner-d tables of any pair by k_wigner_table_dd (hx_mixmat.hip), for the pair tables of the Cl <-> xi columns:
-//   wigner_pair_normalise: (a, b) brought to A >= |B|, A >= 0 by d_{ab} = (-1)^{a-b} d_{ba} = d_{-b,-a} (the pair under which the
-//     mixing-matrix context keeps its tables); returns the sign s with d_{ab} = s d_{AB};
-//   wigner_table_build: out[l * sl + k * sk] = d^l_{ab}(x_k + xlo_k), l = 0 .. lmax (0 below max(|a|, |b|)), device pointers, on the
-//     library stream; complete on return.
-double wigner_pair_normalise(int a, int b, int *A, int *B);
-int wigner_table_build(int lmax, int a, int b, int n, const double *d_x, const double *d_xlo, double *d_out, long long sl, long long sk);
-// hx_transforms.hip: the cached table [lmax + 1][kpad] of the normalised pair (A, B) at the lmax + 1 Gauss-Legendre nodes and their
-// weights w, for hx_xi_cols.hip (built on first use; see PairCache for how long the pointers hold)
+// hx_transforms.hip: the cached table [lmax + 1][kpad] of the normalised pair (A, B) (wigner_pair_normalise, hx_wigner.h) at the lmax + 1
+// Gauss-Legendre nodes and their weights w, for hx_xi_cols.hip (built on first use; see PairCache for how long the pointers hold)
 int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **w, int *kpad);
 
 // The two halves of hx_pointsht_adjoint (hx_nufft.hip), for callers that keep grids resident (hx_catalm, hx_mapper.hip).

@@ -40,6 +40,7 @@
 #include "hx_sht_common.h"
 
 #include "hx_sort.h"
+#include "hx_wigner.h"
 
 using namespace hx;
 using namespace hxfft;
@@ -483,7 +484,7 @@ __global__ __launch_bounds__(256) void k_nufft_gather_tiles(long long npts, cons
 // 1.1e-16 / sin(theta) only, and the error is the same at every l: l * 1.1e-16 / sin(theta_ring) of a value, 4e-11 of the largest value
 // at lmax 4200 (theta_0 = pi / N = 1.9e-4) for a point that lies among those rings.  The adjoint lives with it (its tests give such points a
 // wider bound); here the modes of the NUFFT_POLAR_K ring pairs next to the poles are formed again from Wigner-d tables built in
-// double-double at the nodes x + xlo (wigner_table_build, hx_mixmat.hip: the tables of the mixing matrices), for the orders m <=
+// double-double at the nodes x + xlo (wigner_table_build, hx_wigner.hip: the tables of the mixing matrices), for the orders m <=
 // NUFFT_POLAR_M, and overwrite what the sweep left:
 //     (+-s)lambda_lm(theta) = (-1)^m N_l d^l_{m,-+s}(theta),  N_l = sqrt((2l+1)/4pi)     (s = 0: lambda_lm = (-1)^m N_l d^l_{m0}),
 //     P+ = -(-1)^m sum_l N_l d^l_{m,-s} (E + iB),  P- = -(-1)^(m+s) sum_l N_l d^l_{m,+s} (E - iB),  Q = (P+ + P-) / 2,  U = (P+ - P-) / 2i,

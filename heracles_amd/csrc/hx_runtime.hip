@@ -488,6 +488,21 @@ int hx_init(int device)
     return HX_OK;
 }
 
+// Everything the library keeps in HBM between calls outside a plan or a context: the one-shot mixing-matrix cache of hx_mixmat.hip
+// (the context of the last (l1max, l2max, l3max) with its tables and staged mask spectrum, the staging buffer of a host destination --
+// which hx_mixctx_apply shares --: ~3 GB at L = 6144), the buffers of hx_alm2cl_pairs (tables, partial sums, staging: up to 512 MB) and
+// the nodes, weights and Wigner tables hx_cl2corr / hx_corr2cl keep for their last lmax (4 (lmax + 1) ceil64(lmax + 1) doubles: 1.2 GB at
+// lmax 6144, 4.9 GB at 12288).  The next call allocates again.
+int hx_release_caches(void)
+{
+    if (rt().ready) (void)hipStreamSynchronize(rt().stream);
+    mixmat_drop_cache();
+    alm2cl_drop_cache();
+    corr_cache_drop();
+    synalm_drop_cache();
+    return HX_OK;
+}
+
 int hx_set_stream(void *stream)
 {
     HX_TRY(ensure_ready());

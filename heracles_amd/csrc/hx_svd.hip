@@ -17,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "hx_common.h"
+#include "hx_gemm.h"
 
 namespace hx {
 

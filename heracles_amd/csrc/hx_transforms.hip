@@ -9,10 +9,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <memory>
 #include <vector>
 
-#include "hx_common.h"
+#include "hx_wigner.h"
 
 namespace hx {
 
@@ -120,8 +119,9 @@ __global__ __launch_bounds__(256) void k_corr2cl(int lmax, int n, int kpad, cons
 
 
 struct CorrCache {
-    int lmax = -1, n = 0, kpad = 0;
-    DevBuf x, w, T;
+    int lmax = -1, kpad = 0;
+    GLNodes gl;  // the lmax + 1 nodes and weights (no low parts)
+    DevBuf T;
 };
 
 static int corr_tables(int lmax, CorrCache &c)
@@ -129,18 +129,16 @@ static int corr_tables(int lmax, CorrCache &c)
     if (c.lmax == lmax && c.T.p) return HX_OK;
     const int n = lmax + 1, kpad = (n + 63) / 64 * 64;
     c.lmax = -1;  // (a build that fails half-way leaves no size behind that the buffers no longer hold)
-    HX_TRY(c.x.alloc(sizeof(double) * n));
-    HX_TRY(c.w.alloc(sizeof(double) * n));
+    HX_TRY(c.gl.ensure(n, false));
     HX_TRY(c.T.alloc(sizeof(double) * (size_t)4 * (lmax + 1) * kpad));
     hipStream_t st = rt().stream;
-    HX_TRY(launch_gauss_legendre(n, c.x.as<double>(), c.w.as<double>()));
     HX_HIP(hipMemsetAsync(c.T.p, 0, sizeof(double) * (size_t)4 * (lmax + 1) * kpad, st));
     {
         ProfScope ps("wigner_tables");
-        hipLaunchKernelGGL(k_corr_tables, dim3((n + 63) / 64), dim3(64), 0, st, lmax, n, kpad, c.x.as<double>(), c.T.as<double>());
+        hipLaunchKernelGGL(k_corr_tables, dim3((n + 63) / 64), dim3(64), 0, st, lmax, n, kpad, c.gl.x.as<double>(), c.T.as<double>());
     }
     HX_HIP(hipGetLastError());
-    c.lmax = lmax; c.n = n; c.kpad = kpad;
+    c.lmax = lmax; c.kpad = kpad;
     return HX_OK;
 }
 
@@ -157,7 +155,7 @@ int corr_tables_view(int lmax, const double **T, const double **w, int *kpad)
     CorrCache &c = corr_cache();
     HX_TRY(corr_tables(lmax, c));
     *T = c.T.as<double>();
-    *w = c.w.as<double>();
+    *w = c.gl.w.as<double>();
     *kpad = c.kpad;
     return HX_OK;
 }
@@ -169,16 +167,9 @@ int corr_tables_view(int lmax, const double **T, const double **w, int *kpad)
 // (A >= |B|, wigner_pair_normalise): (a, b), (b, a), (-b, -a) and (-a, -b) share one table and the caller applies the sign that
 // normalisation leaves.  At most max_tabs tables are kept (env HX_XI_TABLES at first use, default 8, at least 2: a four-column key
 // reads two), the one used longest ago is dropped for a new one; another lmax drops them all.
-struct PairTable {
-    int a = 0, b = 0;
-    DevBuf T;
-    unsigned long long used = 0;
-};
 struct PairCache {
-    int lmax = -1, n = 0, kpad = 0, max_tabs = 0;
-    DevBuf x, xlo, w;
-    std::vector<std::unique_ptr<PairTable>> tabs;
-    unsigned long long tick = 0;
+    GLNodes gl;
+    WigTableSet set;  // (lmax = -1: nothing held)
 };
 
 static PairCache &pair_cache()
@@ -189,12 +180,10 @@ static PairCache &pair_cache()
 
 static void pair_cache_clear(PairCache &c)
 {
-    c.tabs.clear();
-    c.x.release();
-    c.xlo.release();
-    c.w.release();
-    c.lmax = -1;
-    c.n = c.kpad = 0;
+    c.set.tabs.clear();
+    c.gl.release();
+    c.set.lmax = -1;
+    c.set.rows = c.set.kpad = 0;
 }
 
 // *T holds until the next call of this function with a pair that is not cached, *w until the next call with another lmax (or
@@ -203,45 +192,22 @@ static void pair_cache_clear(PairCache &c)
 int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **w, int *kpad)
 {
     PairCache &c = pair_cache();
-    hipStream_t st = rt().stream;
-    if (!c.max_tabs) {
-        c.max_tabs = 8;
-        if (const char *e = getenv("HX_XI_TABLES")) c.max_tabs = std::max(2, atoi(e));
+    WigTableSet &s = c.set;
+    if (!s.max_tabs) {
+        s.max_tabs = 8;
+        if (const char *e = getenv("HX_XI_TABLES")) s.max_tabs = std::max(2, atoi(e));
     }
-    if (c.lmax != lmax || !c.w.p) {
-        HX_HIP(hipStreamSynchronize(st));
+    if (s.lmax != lmax || !c.gl.w.p) {
+        HX_HIP(hipStreamSynchronize(rt().stream));
         pair_cache_clear(c);
-        const int n = lmax + 1;
-        HX_TRY(c.x.alloc(sizeof(double) * n));
-        HX_TRY(c.xlo.alloc(sizeof(double) * n));
-        HX_TRY(c.w.alloc(sizeof(double) * n));
-        HX_TRY(launch_gauss_legendre(n, c.x.as<double>(), c.w.as<double>(), c.xlo.as<double>()));
-        c.lmax = lmax; c.n = n; c.kpad = (n + 63) / 64 * 64;
+        HX_TRY(c.gl.ensure(lmax + 1, true));
+        s.lmax = lmax; s.rows = lmax + 1; s.kpad = (lmax + 1 + 63) / 64 * 64;
     }
-    *w = c.w.as<double>();
-    *kpad = c.kpad;
-    for (auto &t : c.tabs)
-        if (t->a == A && t->b == B) {
-            t->used = ++c.tick;
-            *T = t->T.as<double>();
-            return HX_OK;
-        }
-    if ((int)c.tabs.size() >= c.max_tabs) {
-        size_t old = 0;
-        for (size_t i = 1; i < c.tabs.size(); ++i)
-            if (c.tabs[i]->used < c.tabs[old]->used) old = i;
-        HX_HIP(hipStreamSynchronize(st));  // (a launch may still be reading it)
-        c.tabs.erase(c.tabs.begin() + old);
-    }
-    std::unique_ptr<PairTable> t(new PairTable);
-    t->a = A; t->b = B;
-    const size_t bytes = sizeof(double) * (size_t)(lmax + 1) * c.kpad;
-    HX_TRY(t->T.alloc(bytes));
-    HX_HIP(hipMemsetAsync(t->T.p, 0, bytes, st));
-    HX_TRY(wigner_table_build(lmax, A, B, c.n, c.x.as<double>(), c.xlo.as<double>(), t->T.as<double>(), (long long)c.kpad, 1LL));
-    t->used = ++c.tick;
+    *w = c.gl.w.as<double>();
+    *kpad = s.kpad;
+    WigTable *t = nullptr;
+    HX_TRY(s.get(c.gl, A, B, &t));
     *T = t->T.as<double>();
-    c.tabs.push_back(std::move(t));
     return HX_OK;
 }
 
@@ -250,11 +216,10 @@ int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **
 void corr_cache_drop()
 {
     CorrCache &c = corr_cache();
-    c.x.release();
-    c.w.release();
+    c.gl.release();
     c.T.release();
     c.lmax = -1;
-    c.n = c.kpad = 0;
+    c.kpad = 0;
     pair_cache_clear(pair_cache());
 }
 
@@ -273,7 +238,7 @@ extern "C" int hx_cl2corr(int lmax, int nspec, const double *cls, double *corrs)
     OutView vo;
     HX_TRY(vi.bind(cls, sz));
     HX_TRY(vo.bind(corrs, sz));
-    hipLaunchKernelGGL(k_cl2corr, dim3((c.n + 63) / 64, nspec), dim3(64), 0, rt().stream, lmax, c.n, c.kpad, nspec,
+    hipLaunchKernelGGL(k_cl2corr, dim3((c.gl.n + 63) / 64, nspec), dim3(64), 0, rt().stream, lmax, c.gl.n, c.kpad, nspec,
                        c.T.as<double>(), vi.as<double>(), vo.as<double>());
     HX_HIP(hipGetLastError());
     HX_TRY(vo.finish());
@@ -292,8 +257,8 @@ extern "C" int hx_corr2cl(int lmax, int nspec, const double *corrs, double *cls)
     OutView vo;
     HX_TRY(vi.bind(corrs, sz));
     HX_TRY(vo.bind(cls, sz));
-    hipLaunchKernelGGL(k_corr2cl, dim3(lmax + 1, nspec), dim3(256), 0, rt().stream, lmax, c.n, c.kpad, c.T.as<double>(),
-                       c.w.as<double>(), vi.as<double>(), vo.as<double>());
+    hipLaunchKernelGGL(k_corr2cl, dim3(lmax + 1, nspec), dim3(256), 0, rt().stream, lmax, c.gl.n, c.kpad, c.T.as<double>(),
+                       c.gl.w.as<double>(), vi.as<double>(), vo.as<double>());
     HX_HIP(hipGetLastError());
     HX_TRY(vo.finish());
     HX_HIP(hipStreamSynchronize(rt().stream));

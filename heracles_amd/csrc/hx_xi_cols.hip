@@ -25,7 +25,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "hx_common.h"
+#include "hx_wigner.h"
 
 namespace hx {
 namespace {

@@ -295,6 +295,45 @@ def test_context_drops_and_rebuilds_tables(monkeypatch):
             np.testing.assert_array_equal(ctx(cl, sp), m, err_msg=str(sp))
 
 
+def test_context_restages_spectra_of_other_lengths():
+    """One context fed a spectrum longer than l3max + 1, then a shorter one, then the first again: the mask spectrum staged inside the
+    context is truncated / zero-padded anew every time (no stale tail), and host and device destinations get the same bits, which
+    are those of a fresh one-shot build; so are the binned rows of the short spectrum against a fresh context."""
+    import torch
+
+    import heracles_amd as hx
+    from heracles_amd import _lib
+    from heracles_amd.binning import BinPlan
+
+    L = 40
+    kw = {"l1max": 20, "l2max": 22, "l3max": L}
+    long_, short = _cl(59, seed=21), _cl(11, seed=22)
+    assert long_.size == 60 > L + 1 > short.size == 12
+    plan = BinPlan(np.arange(21), np.array([2, 5, 9, 14, 21]), "2l+1")
+    with hx.MixmatContext(20, 22, L) as ctx, hx.MixmatContext(20, 22, L) as fresh:
+        ctx.set_bins(plan)
+        fresh.set_bins(plan)
+        for spin in [(0, 0), (2, 0), (3, 1)]:
+            for cl in (long_, short, long_):
+                got = ctx(cl, spin)
+                hx.mixmat_release()  # (the one-shot entry points keep a context of their own: drop it, so that this one is fresh)
+                np.testing.assert_array_equal(got, hx_any(cl, spin, **kw), err_msg=f"{spin} {cl.size}")
+                # the spectrum from device memory takes the other staging path (memset + device copy) in the same context
+                src = torch.as_tensor(cl, device="cuda")
+                from_dev = np.full(got.shape, np.nan)
+                _lib.check(_lib.load().hx_mixctx_apply_spin(ctx._h, _lib.ptr(src), cl.size, spin[0], spin[1], _lib.ptr(from_dev)))
+                np.testing.assert_array_equal(from_dev, got, err_msg=f"{spin} {cl.size} device spectrum")
+                dev = torch.full(got.shape, float("nan"), dtype=torch.float64, device="cuda")
+                assert ctx(cl, spin, out=dev) is dev
+                np.testing.assert_array_equal(dev.cpu().numpy(), got, err_msg=f"{spin} {cl.size} device")
+                dev.fill_(float("nan"))
+                hx_any(cl, spin, out=dev, **kw)
+                np.testing.assert_array_equal(dev.cpu().numpy(), got, err_msg=f"{spin} {cl.size} one-shot, device")
+            # `fresh` never sees the long spectrum
+            np.testing.assert_array_equal(ctx(short, spin), fresh(short, spin), err_msg=str(spin))
+            np.testing.assert_array_equal(ctx.binned(short, spin), fresh.binned(short, spin), err_msg=str(spin))
+
+
 # ---- 7. old and new entry points ----------------------------------------------------------------------------------------------------
 def test_old_and_new_entry_points_agree():
     import heracles_amd as hx
