@@ -43,6 +43,7 @@ from .fields import (
 from .mapping import catalog_alms, map_catalogs, transform
 from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
 from .regions import jackknife_regions
+from .rotation import coord_matrix, euler_from_matrix, matrix_from_euler, rotate_alm, rotate_alms
 from .sht import Plan, get_plan
 from .transforms import cl2corr, cl2corr_columns, corr2cl, corr2cl_columns, gauss_legendre, wigner_d_table
 from .fits import read_vmap
@@ -74,5 +75,5 @@ __all__ = [
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
     "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
     "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
-    "jackknife_regions",
+    "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
 ]

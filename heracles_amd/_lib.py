@@ -34,7 +34,7 @@ SYMBOLS = (
     "hx_pixel_weights_size", "hx_pixel_weights_expand", "hx_pixel_weights_solve",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
-    "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions",
+    "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
     "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
     "hx_catmap_create_sel", "hx_catmap_page_sel", "hx_catmap_moments_sel", "hx_catmap_finish_sel", "hx_catmap_destroy_sel",
@@ -169,6 +169,7 @@ def load():
         L.hx_mockcat_counts.argtypes = [i, C.c_int64, C.c_int64, dp, C.c_uint64, C.c_uint32, vp, C.POINTER(C.c_int64)]
         L.hx_mockcat_points.argtypes = [i, C.c_int64, C.c_int64, vp, C.c_uint64, C.c_uint32, i, dp, dp, dp, dp, dp, vp]
         L.hx_jk_regions.argtypes = [i, dp, i, vp, dp, dp]
+        L.hx_rotate_alm.argtypes = [i, i, dp, dp, C.c_double, C.c_double, C.c_double]
         L.hx_catmap_create.restype = vp
         L.hx_catmap_create.argtypes = [C.c_int64, i, i, vp, vp]
         L.hx_catmap_page.argtypes = [vp, C.c_int64, vp]

@@ -580,6 +580,21 @@ int hx_mockcat_points(int nside, int64_t pix_begin, int64_t pix_end, const int64
  * than njk, njk or nside out of range.  Host or device pointers, as everywhere in this header. */
 int hx_jk_regions(int nside, const double *weight, int njk, int32_t *labels, double *region_weight, double *axes);
 
+/* ---- rotation of alms by any Euler angles ---------------------------------------------------------------------------
+ * R = Rz(phi) Ry(theta) Rz(psi) on column vectors (psi about z first, then theta about y, then phi about z; counter-clockwise about
+ * the fixed axes), rotated field f'(n) = f(R^-1 n):
+ *   alm_out[c][l, m] = sum_{m' = -l .. l} exp(-i m phi) d^l_{mm'}(theta) exp(-i m' psi) alm_in[c][l, m'],
+ * d^l(theta) = exp(-i theta J_y) in the Condon-Shortley basis (d^1_10 = -sin(theta) / sqrt(2)), a_l,-m' = (-1)^m' conj(a_lm'); the
+ * imaginary part of a_l0 is not read and comes back as exactly 0.  alm_in, alm_out: (ncomp, nlm) complex128 in the layout of every alm
+ * here (m-major, mmax = lmax); every component is rotated with the same matrices (E and B of a field of any spin weight rotate as
+ * scalars).  Any finite angles: theta is brought into [0, pi] on the host ((psi, theta, phi) -> (psi - pi, -theta, phi + pi)),
+ * theta = 0 and theta = pi take their closed forms.  The sum over m' has a fixed order: the result is bit-identical from call to call
+ * and does not depend on how the components are batched.
+ * Host or device pointers, as everywhere in this header.  The two arrays must not overlap (every output order needs every input
+ * order): HX_ERR_ARG, as are lmax < 0, ncomp < 1 and an angle that is NaN or Inf; lmax > 32000 is HX_ERR_UNSUPPORTED.  Runs on the
+ * library stream; its flops are added to the vector-unit figure of hx_executed_flops; profile name "rotate_alm". */
+int hx_rotate_alm(int lmax, int ncomp, const double _Complex *alm_in, double _Complex *alm_out, double psi, double theta, double phi);
+
 #ifdef __cplusplus
 }
 #endif
