@@ -47,6 +47,7 @@ from .rotation import coord_matrix, euler_from_matrix, matrix_from_euler, rotate
 from .sht import Plan, get_plan
 from .transforms import cl2corr, cl2corr_columns, corr2cl, corr2cl_columns, gauss_legendre, wigner_d_table
 from .fits import read_vmap
+from .gausscov import covariance_requests, gaussian_covariance_coupled, mask_product_cls, table_key
 from .twopoint import (
     alm2cl,
     alm2cl_pairs,
@@ -76,4 +77,5 @@ __all__ = [
     "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
     "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
     "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
+    "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
 ]

@@ -34,11 +34,17 @@ SYMBOLS = (
     "hx_pixel_weights_size", "hx_pixel_weights_expand", "hx_pixel_weights_solve",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
-    "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm",
+    "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm", "hx_gauss_cov_accumulate",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
     "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
     "hx_catmap_create_sel", "hx_catmap_page_sel", "hx_catmap_moments_sel", "hx_catmap_finish_sel", "hx_catmap_destroy_sel",
 )
+
+
+class CovItem(C.Structure):
+    """hx_cov_item: one block of hx_gauss_cov_accumulate -- its corner and the spectra of its two products (s[2] < 0: one)."""
+
+    _fields_ = [("row", C.c_int64), ("col", C.c_int64), ("s", C.c_int * 4)]
 
 
 class HxError(RuntimeError):
@@ -170,6 +176,7 @@ def load():
         L.hx_mockcat_points.argtypes = [i, C.c_int64, C.c_int64, vp, C.c_uint64, C.c_uint32, i, dp, dp, dp, dp, dp, vp]
         L.hx_jk_regions.argtypes = [i, dp, i, vp, dp, dp]
         L.hx_rotate_alm.argtypes = [i, i, dp, dp, C.c_double, C.c_double, C.c_double]
+        L.hx_gauss_cov_accumulate.argtypes = [i, dp, i, dp, i, vp, vp, vp, C.c_int64, vp, dp, C.c_int64]
         L.hx_catmap_create.restype = vp
         L.hx_catmap_create.argtypes = [C.c_int64, i, i, vp, vp]
         L.hx_catmap_page.argtypes = [vp, C.c_int64, vp]
@@ -273,8 +280,9 @@ def release_caches():
     the last sizes + host-staging buffer, ~3 GB at L = 6144), the buffers of ``alm2cl_pairs`` (<= 512 MB) and the nodes, weights and
     Wigner tables ``cl2corr`` / ``corr2cl`` / ``naturalspice`` keep for their last lmax (1.2 GB at lmax 6144; the column transforms of
     ``naturalspice_batch`` read the same tables and keep nothing of their own; with ``exact_spin`` up to ``HX_XI_TABLES`` pair tables of
-    0.31 GB each at lmax 6144 lie beside them), the Cholesky factor ``synalm`` keeps (23 MB at 30 components and lmax 6144):
-    hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
+    0.31 GB each at lmax 6144 lie beside them), the Cholesky factor ``synalm`` keeps (23 MB at 30 components and lmax 6144), the folded
+    coupling tables of ``gaussian_covariance_coupled`` ((spectra + 1) x bins x (lmax + 1) doubles: 0.22 GB at 465 spectra, 31 bins,
+    lmax 2048): hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
     per result) go with them."""
     from . import weights
 

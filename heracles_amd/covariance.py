@@ -441,11 +441,17 @@ def flatten(results, order=None):
 
 
 # ---- Gaussian target and shrinkage -------------------------------------------------------------------------------------------------
+def _with_bias(cls):
+    """The fiducial spectra of the Gaussian covariances: every spectrum with its ``bias`` metadata added to every element
+    (heracles/dices/shrinkage.py:112-116); shared by ``gaussian_covariance`` and ``gausscov.gaussian_covariance_coupled``."""
+    bs = bias(cls)
+    return {key: replace(res, array=res.array + bs[key]) for key, res in cls.items()}
+
+
 def gaussian_covariance(cls):
     """Gaussian covariance of the spectra (heracles/dices/shrinkage.py:101-144), as the reference computes it: the auto-spectrum
     ``bias`` metadata added to every element, C(a1 a2) C(b1 b2) + C(a1 b2) C(b1 a2) on the l diagonal, no 1 / (2l + 1)."""
-    bs = bias(cls)
-    cls = {key: replace(res, array=res.array + bs[key]) for key, res in cls.items()}
+    cls = _with_bias(cls)
     cov = {}
     for k1, k2 in itertools.combinations_with_replacement(list(cls), 2):
         a1, b1, i1, j1 = k1

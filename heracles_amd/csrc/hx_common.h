@@ -128,6 +128,8 @@ void alm2cl_drop_cache();  // hx_twopoint.hip: the buffers hx_alm2cl_pairs keeps
 void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner tables hx_cl2corr / hx_corr2cl keep for the last lmax
 void synalm_drop_cache();  // hx_synalm.hip: the factor hx_synalm / hx_cl_cholesky keep between calls
 int rotate_exec_flops(unsigned long long *v, bool reset);  // hx_rotate.hip: FP64 vector flops hx_rotate_alm executed (for hx_executed_flops)
+void gausscov_drop_cache();  // hx_gausscov.hip: the folded tables Z and coefficients hx_gauss_cov_accumulate keeps between calls
+int gausscov_exec_flops(unsigned long long *v, bool reset);  // hx_gausscov.hip: FP64 vector flops of hx_gauss_cov_accumulate (for hx_executed_flops)
 
 int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  // hx_transforms.hip: those tables, for hx_xi_cols.hip
 // hx_transforms.hip: the cached table [lmax + 1][kpad] of the normalised pair (A, B) (wigner_pair_normalise, hx_wigner.h) at the lmax + 1

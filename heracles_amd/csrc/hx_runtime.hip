@@ -476,6 +476,7 @@ int hx_init(int device)
         mixmat_drop_cache();
         alm2cl_drop_cache();
         synalm_drop_cache();
+        gausscov_drop_cache();
         stager_reset_events();
     }
     HX_HIP(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
@@ -500,6 +501,7 @@ int hx_release_caches(void)
     alm2cl_drop_cache();
     corr_cache_drop();
     synalm_drop_cache();
+    gausscov_drop_cache();
     return HX_OK;
 }
 

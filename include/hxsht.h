@@ -595,6 +595,29 @@ int hx_jk_regions(int nside, const double *weight, int njk, int32_t *labels, dou
  * library stream; its flops are added to the vector-unit figure of hx_executed_flops; profile name "rotate_alm". */
 int hx_rotate_alm(int lmax, int ncomp, const double _Complex *alm_in, double _Complex *alm_out, double psi, double theta, double phi);
 
+/* ---- mask-aware Gaussian covariance of pseudo-Cl, narrow-kernel approximation ---------------------------------------
+ * One coupling table and a list of spectra into blocks of the covariance of the (binned) data vector.  With Xi_{ll'} = g00[l][l'] /
+ * (2l' + 1) and Sbar^s_{ll'} = (spec[s][l] + spec[s][l']) / 2, every item adds its block
+ *   cov[(row + b) ldc + col + b'] += sum_{l in b, l' in b'} w_l w_l' Xi_{ll'} (Sbar^{s0} Sbar^{s1} + Sbar^{s2} Sbar^{s3}) / (norm_b norm_b')
+ * and the call touches no other element.  s[2] < 0: the first product only.
+ *   g00   : (lmax + 1)^2, the (0,0) matrix as hx_mixctx_apply (kind 1) writes it for the cross-spectrum of two mask products; the call
+ *           divides the column factor out itself.  Xi is taken as symmetric (it is, to rounding, for l1max = l2max).
+ *   spec  : [nspec][lmax + 1].
+ *   which, w, norm : the bins of both axes as in hx_mixctx_set_bins, HOST arrays; an empty bin adds nothing.  nbins = 0: every l is
+ *           its own bin with weight 1 (blocks of edge lmax + 1), formed element by element.
+ *   items : HOST array; the blocks of one call must not overlap (HX_ERR_ARG: each element has one owner; use two calls).
+ *   cov   : DEVICE memory, leading dimension ldc.  g00 and spec host or device.
+ * Binned calls fold the table once per call into Z[s][b'][l] = sum_{l' in b'} w_l' Xi_{ll'} S^s_l' for the spectra the items name and
+ * the all-ones spectrum, then form each element from those rows: L^2 nspec + nitem nbins L operations instead of nitem L^2.  Z
+ * ((named spectra + 1) x nbins x (lmax + 1) doubles) stays in HBM until hx_release_caches; HX_ERR_MEM, nothing written, if it does not
+ * fit in 0.9 of the free memory.  No floating-point atomics: a block has the same bits in every run and whatever other items share
+ * the call.  HX_ERR_ARG, nothing written: a null pointer, a spectrum index outside [0, nspec), a block that leaves ldc, a negative
+ * row or col, which[l] outside [-1, nbins), a zero or non-finite norm of a bin with members.  Runs on the library stream; its flops
+ * (counted from the launch shapes) are added to the vector-unit figure of hx_executed_flops; profile name "gauss_cov". */
+typedef struct { int64_t row, col; int s[4]; } hx_cov_item;
+int hx_gauss_cov_accumulate(int lmax, const double *g00, int nspec, const double *spec, int nbins, const int *which, const double *w,
+                            const double *norm, int64_t nitem, const hx_cov_item *items, double *cov, int64_t ldc);
+
 #ifdef __cplusplus
 }
 #endif
