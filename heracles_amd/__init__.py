@@ -40,6 +40,7 @@ from .fields import (
     Weights,
     get_masks,
 )
+from .masks import apodize_mask, mask_discs, mask_distance
 from .mapping import catalog_alms, map_catalogs, transform
 from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
 from .regions import jackknife_regions
@@ -78,4 +79,5 @@ __all__ = [
     "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
     "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
     "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
+    "mask_discs", "mask_distance", "apodize_mask",
 ]

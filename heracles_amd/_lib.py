@@ -35,6 +35,7 @@ SYMBOLS = (
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
     "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm", "hx_gauss_cov_accumulate",
+    "hx_mask_discs", "hx_mask_distance", "hx_mask_taper",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
     "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
     "hx_catmap_create_sel", "hx_catmap_page_sel", "hx_catmap_moments_sel", "hx_catmap_finish_sel", "hx_catmap_destroy_sel",
@@ -177,6 +178,9 @@ def load():
         L.hx_jk_regions.argtypes = [i, dp, i, vp, dp, dp]
         L.hx_rotate_alm.argtypes = [i, i, dp, dp, C.c_double, C.c_double, C.c_double]
         L.hx_gauss_cov_accumulate.argtypes = [i, dp, i, dp, i, vp, vp, vp, C.c_int64, vp, dp, C.c_int64]
+        L.hx_mask_discs.argtypes = [i, dp, C.c_int64, dp, dp, dp, C.c_double]
+        L.hx_mask_distance.argtypes = [i, dp, C.c_double, dp]
+        L.hx_mask_taper.argtypes = [i, dp, C.c_double, i, dp]
         L.hx_catmap_create.restype = vp
         L.hx_catmap_create.argtypes = [C.c_int64, i, i, vp, vp]
         L.hx_catmap_page.argtypes = [vp, C.c_int64, vp]

@@ -618,6 +618,27 @@ typedef struct { int64_t row, col; int s[4]; } hx_cov_item;
 int hx_gauss_cov_accumulate(int lmax, const double *g00, int nspec, const double *spec, int nbins, const int *which, const double *w,
                             const double *norm, int64_t nitem, const hx_cov_item *items, double *cov, int64_t ldc);
 
+/* ---- mask tools: disc holes, distance to the nearest masked pixel, C1 / C2 apodisation ------------------------------
+ * Maps are RING, float64, nside 1 .. 8192 (any integer).  The centre v_p of pixel p is the pixel centre of the HEALPix paper; between
+ * unit vectors h(u, v) = ((u_x - v_x)^2 + (u_y - v_y)^2 + (u_z - v_z)^2) / 2 = 1 - cos(angle), for an angle h(a) = 2 sin^2(a / 2); a
+ * pixel is masked when mask[p] <= 0.  All angles in degrees.  A NaN or infinite mask value (hx_last_error names the first such
+ * pixel), nside out of range, a null pointer: HX_ERR_ARG, nothing is written.  Host or device pointers, as everywhere in this header.
+ * hx_mask_discs: mask[p] = 0.0 wherever h(v_p, c_k) <= h(radius_k) for some disc k, c_k = (cos lat cos lon, cos lat sin lon, sin lat):
+ *   the pixel centres inside the discs (query_disc, inclusive = False).  mask is changed in place.  radius: [ndisc], or NULL for
+ *   radius_all on every disc.  The result does not depend on the order of the discs and is bit-identical from run to run.  ndisc = 0
+ *   writes nothing.  HX_ERR_ARG, nothing written: a NaN or infinite coordinate, |lat| > 90, a radius outside [0, 180]
+ *   (hx_last_error names the first such disc).  HX_MASK_WIDE=1 (tests) sends every disc down the work-group-per-disc path.
+ * hx_mask_distance: H[p] = min(h(max_distance), min over masked q of h(v_p, v_q)), 0 on masked pixels, the cap everywhere for a mask
+ *   without masked pixels; the angle is 2 asin(sqrt(H / 2)).  max_distance in (0, 180].
+ * hx_mask_taper: out[p] = mask[p] w(sqrt(H[p] / h(aposize))) with H capped at h(aposize), 0.0 on masked pixels; kind 1 (C1):
+ *   w = x - sin(2 pi x) / (2 pi); kind 2 (C2): w = (1 - cos(pi x)) / 2 -- NaMaster's mask_apodization of those names.  aposize in
+ *   (0, 180]; any other kind is HX_ERR_ARG.  out may be mask itself (any other overlap is HX_ERR_ARG).
+ * Both are bit-identical from run to run (a minimum does not depend on the order).  Profile names "mask_discs", "mask_neighbours",
+ * "mask_distance". */
+int hx_mask_discs(int nside, double *mask, int64_t ndisc, const double *lon, const double *lat, const double *radius, double radius_all);
+int hx_mask_distance(int nside, const double *mask, double max_distance, double *H);
+int hx_mask_taper(int nside, const double *mask, double aposize, int kind, double *out);
+
 #ifdef __cplusplus
 }
 #endif
