@@ -41,6 +41,7 @@ from .fields import (
     get_masks,
 )
 from .masks import apodize_mask, mask_discs, mask_distance
+from .deprojection import DeprojectionInfo, deproject_maps, deproject_templates, deprojection_bias
 from .mapping import catalog_alms, map_catalogs, transform
 from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
 from .regions import jackknife_regions
@@ -80,4 +81,5 @@ __all__ = [
     "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
     "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
     "mask_discs", "mask_distance", "apodize_mask",
+    "deproject_templates", "deproject_maps", "deprojection_bias", "DeprojectionInfo",
 ]

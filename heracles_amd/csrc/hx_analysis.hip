@@ -1409,16 +1409,17 @@ extern "C" int hx_executed_flops(double *out2, int reset)
     if (!out2) return fail(HX_ERR_ARG, "hx_executed_flops: null output");
     HX_TRY(ensure_ready());
     HX_HIP(hipStreamSynchronize(rt().stream));
-    unsigned long long v[2] = {0, 0}, w = 0, wr = 0, wg = 0;
+    unsigned long long v[2] = {0, 0}, w = 0, wr = 0, wg = 0, wd = 0;
     HX_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_exec_flops), sizeof(v)));
     HX_TRY(valu_exec_flops(&w, reset != 0));
     HX_TRY(rotate_exec_flops(&wr, reset != 0));  // (hx_rotate_alm: recurrences and accumulation, all on the vector unit)
     HX_TRY(gausscov_exec_flops(&wg, reset != 0));  // (hx_gauss_cov_accumulate: folds and block sums, all on the vector unit)
+    HX_TRY(deproject_exec_flops(&wd, reset != 0));  // (hx_deproject_gram: matrix instructions, counted from the launch shape)
     if (reset) {
         const unsigned long long z[2] = {0, 0};
         HX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_exec_flops), z, sizeof(z)));
     }
-    out2[0] = (double)v[0];
+    out2[0] = (double)v[0] + (double)wd;
     out2[1] = (double)v[1] + (double)w + (double)wr + (double)wg;
     return HX_OK;
 }

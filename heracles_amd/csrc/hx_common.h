@@ -131,6 +131,9 @@ int rotate_exec_flops(unsigned long long *v, bool reset);  // hx_rotate.hip: FP6
 void gausscov_drop_cache();  // hx_gausscov.hip: the folded tables Z and coefficients hx_gauss_cov_accumulate keeps between calls
 int gausscov_exec_flops(unsigned long long *v, bool reset);  // hx_gausscov.hip: FP64 vector flops of hx_gauss_cov_accumulate (for hx_executed_flops)
 
+void deproject_drop_cache();  // hx_deproject.hip: the partial tiles and the reduced matrix hx_deproject_gram keeps between calls
+int deproject_exec_flops(unsigned long long *v, bool reset);  // hx_deproject.hip: FP64 matrix-instruction flops of hx_deproject_gram (for hx_executed_flops)
+
 int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  // hx_transforms.hip: those tables, for hx_xi_cols.hip
 // hx_transforms.hip: the cached table [lmax + 1][kpad] of the normalised pair (A, B) (wigner_pair_normalise, hx_wigner.h) at the lmax + 1
 // Gauss-Legendre nodes and their weights w, for hx_xi_cols.hip (built on first use; see PairCache for how long the pointers hold)

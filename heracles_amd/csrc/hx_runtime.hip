@@ -477,6 +477,7 @@ int hx_init(int device)
         alm2cl_drop_cache();
         synalm_drop_cache();
         gausscov_drop_cache();
+        deproject_drop_cache();
         stager_reset_events();
     }
     HX_HIP(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
@@ -502,6 +503,7 @@ int hx_release_caches(void)
     corr_cache_drop();
     synalm_drop_cache();
     gausscov_drop_cache();
+    deproject_drop_cache();
     return HX_OK;
 }
 

@@ -148,13 +148,17 @@ def _debias_cl(cl, bias=None, md=None, *, inplace=False, pixwin=None):
         target = cl.copy()
         update_metadata(target, **meta)
     amount = meta.get("bias") if bias is None else bias
-    if amount is not None:
+    if hasattr(amount, "array") and np.shape(amount.array) == np.shape(target):
+        # a Result of the block's own shape (deprojection_bias): a bias known per component and multipole, in the units of the block
+        target[:] -= np.asarray(amount.array)
+    elif amount is not None:
         target[:] -= _bias_profile(target.shape, meta, amount, pixwin)
     return target
 
 
 def debias_cls(cls, bias=None, *, inplace=False, pixwin=None):
-    """Remove bias from a set of spectra (heracles/twopoint.py:302-313)."""
+    """Remove bias from a set of spectra (heracles/twopoint.py:302-313).  Beyond the reference: an entry of ``bias`` that is a
+    ``Result`` of its block's shape (what ``deprojection_bias`` returns) is subtracted element by element, without the window rule."""
     out = cls if inplace else TocDict()
     for key in cls:
         out[key] = _debias_cl(cls[key], bias and bias.get(key), inplace=inplace, pixwin=pixwin)

@@ -639,6 +639,35 @@ int hx_mask_discs(int nside, double *mask, int64_t ndisc, const double *lon, con
 int hx_mask_distance(int nside, const double *mask, double max_distance, double *H);
 int hx_mask_taper(int nside, const double *mask, double aposize, int kind, double *out);
 
+/* ---- template deprojection of maps ----------------------------------------------------------------------------------
+ * A field's map d (already weighted by its mask v), its templates t_1 .. t_k (unmasked), f_i = v t_i; sums over pixels also run over
+ * the ncomp components (1 for spin 0, else 2).  Maps and templates are [ncomp][npix] arrays, float64; `templates`, `maps` and `out`
+ * are HOST arrays of pointers to them (as hx_alm_subtract); the arrays themselves, mask [npix] (NULL: all ones), gram and alpha are
+ * host or device, as everywhere in this header.
+ * hx_deproject_gram: with the columns X = (v t_1 .. v t_k, d_1 .. d_m), gram = X^T X, the full symmetric n x n matrix, n = ntemp + nmap,
+ *   row-major: G_ij = sum f_i f_j, r_i = sum f_i d for every map, and d^T d.  The inner axis (ncomp npix elements) is cut into slabs
+ *   of max(8192, ceil(ncomp npix / ceil(2048 / tiles))) elements rounded up to a multiple of 32, tiles = T (T + 1) / 2, T = ceil(n / 64):
+ *   a function of the sizes alone.  A slab is accumulated in ascending order on the FP64 matrix unit, the slabs are added in ascending
+ *   order; no floating-point atomics: the same bits in every run and on every device, and gram is exactly symmetric.  HX_DEPROJ_SLAB=n
+ *   (tests, read at every call) sets the slab length.  Partial tiles (tiles x slabs x 32 KiB, at most ~72 MB) and the reduced matrix
+ *   stay in HBM until hx_release_caches; HX_ERR_MEM, nothing written, if they do not fit in 0.9 of the free memory.  HX_ERR_ARG, nothing
+ *   written: npix < 1, ncomp outside {1, 2}, ntemp < 0, nmap < 0, n outside 1 .. 1024, a null pointer, gram overlapping an input, and a
+ *   diagonal entry of the result that is not finite -- hx_last_error names the first such column, a template or a map that holds a NaN
+ *   or an infinite value.  Flops are added to the matrix-unit figure of hx_executed_flops; profile name "deproject_gram".
+ * hx_deproject_apply: out[m][c][p] = maps[m][c][p] - v(p) * (sum_i alpha[m][i] * templates[i][c][p]); the sum starts from 0.0 at i = 0
+ *   and runs in ascending order, every product and every sum rounds on its own (the kernel is compiled with floating-point
+ *   contraction off: no fused multiply-add), the product with v comes last (skipped for mask NULL), the subtraction is separate.
+ *   alpha: [nmap][ntemp].  out[m] may be maps[m] itself; any other overlap of an output with an input or another output is HX_ERR_ARG,
+ *   as are the argument errors above (ntemp 0 .. 1024; nmap = 0 writes nothing).  One streaming pass: a template element is read once
+ *   for up to 8 maps.  Profile name "deproject_apply".
+ * hx_alm_apply_cl: alm_out[x][l, m] = sum_y cl[x][y][l] alm_in[y][l, m]; cl [nout][nin][lmax + 1], alms in the layout of every alm here
+ *   (m-major, mmax = lmax), nin and nout 1 or 2.  Input and output must not overlap (HX_ERR_ARG).  Profile name "alm_apply_cl". */
+int hx_deproject_gram(int64_t npix, int ncomp, int ntemp, const double *const *templates, int nmap, const double *const *maps,
+                      const double *mask, double *gram);
+int hx_deproject_apply(int64_t npix, int ncomp, int ntemp, const double *const *templates, const double *mask, int nmap,
+                       const double *const *maps, const double *alpha, double *const *out);
+int hx_alm_apply_cl(int lmax, int nin, int nout, const double *cl, const double _Complex *alm_in, double _Complex *alm_out);
+
 #ifdef __cplusplus
 }
 #endif
