@@ -21,6 +21,8 @@
 //                   One work-group adds the contributions of a column in one order and one thread owns an output coefficient
 //                   throughout: no atomics on the data, the same bits every call, and a (column, component) pair gets the same
 //                   operations whatever batch it sits in.
+//   Below sin(theta) = ROT_SPLIT_SIN the entry point rotates twice, by (psi, pi/2, 0) and (0, theta - pi/2, phi), through a scratch
+//   alm: d^l(theta) = d^l(pi/2) d^l(theta - pi/2), and FP64 chains lose 1 / sin(theta) of their accuracy.
 //   k_rotate_phase  theta = 0 and theta = pi: d = delta_mm' and d^l_mm'(pi) = (-1)^(l-m') delta_m,-m' leave one phase per order.
 #include <climits>
 #include <cmath>
@@ -35,6 +37,9 @@ constexpr int ROT_MO = 4;   // output columns m per work-group: its waves
 constexpr int ROT_MB = 64;  // pairs (+m', -m') per block: the lanes of the generate phase
 constexpr int ROT_LB = 16;  // multipoles per tile
 constexpr int ROT_LMAX = 32000;  // (l + 1 - m)(l + 1 + m) is formed in 32-bit integers
+// below this sin(theta) a rotation is done as two, by pi/2 and theta - pi/2 (where the FP64 chains of one pass keep a
+// quarter of the 1e-12 contract at lmax 6144)
+constexpr long double ROT_SPLIT_SIN = 0.1L;
 // flops of one pair step of the recurrence (two chains: coefficient 5, fma and product 3, scale 1 each; shared: the products for the
 // square root's argument, its carry and the second coefficient 3, the combination (e, f) 4; the rsqrt itself is not counted) and of
 // one (pair, l, component) of the accumulation (four fmas)
@@ -124,8 +129,8 @@ __global__ __launch_bounds__(ROT_MO * ROT_MB) void k_rotate_alm(RotParams P, int
                 const double vp = ldexp(dcp, ep), vm = ldexp(dcm, em);
                 tile[w][t][lane ^ t] = make_double2(fma(sg, vm, vp), fma(-sg, vm, vp));
                 // l -> l + 1:  s_(l+1) d^(l+1) = ((2l+1)/l) (l(l+1) x - m m') d^l - ((l+1)/l) s_l d^(l-1),  s_l^2 = (l^2 - m^2)(l^2 - m'^2).
-                // l(l+1) x - m m' cancels to a small remainder for m ~ m' ~ l at small theta: both products are exact integers
-                // times x = xh + xl, so one fma rounds the difference itself (at l = 0, m = m' = 0: d^1 = x d^0)
+                // l(l+1) x - m m' cancels to a small remainder for m ~ m' ~ l at small theta.  x = xh + xl with xh a multiple of 2^-22
+                // (the host's split): the inner fma is exact, the outer rounds the difference once (at l = 0, m = m' = 0: d^1 = x d^0)
                 const bool on = l >= l0;
                 const double rl = __shfl(rl_mine, t), lp1 = (double)(l + 1);
                 const double nn = l > 0 ? (double)l * lp1 : 1.0, h2 = l > 0 ? (double)(2 * l + 1) * rl : 1.0, g3 = lp1 * rl;
@@ -244,6 +249,58 @@ double2 split_ld(long double v)
     return make_double2(h, (double)(v - h));
 }
 
+// The tables and parameters of one launch of k_rotate_alm: a rotation by long-double angles, theta in [-pi, pi] (a negative theta
+// is folded as in the entry point).  The buffers live until the caller's call is over.
+struct RotTables {
+    DevBuf psi, phi, lf;
+    RotParams P;
+
+    // share: another launch of the same lmax whose log2 k! table is used instead of building a second one
+    int build(int lmax, long double ps, long double th, long double ph, const RotTables *share = nullptr)
+    {
+        if (th < 0) {
+            th = -th;
+            ps -= PI_L;
+            ph += PI_L;
+        }
+        const size_t nl = (size_t)lmax + 1;
+        if (!share) {
+            std::vector<double2> t(2 * nl);
+            long double sum = 0, comp = 0;  // log2 k!, compensated
+            t[0] = make_double2(0.0, 0.0);
+            for (size_t k = 1; k < t.size(); ++k) {
+                const long double y = log2l((long double)k) - comp, s = sum + y;
+                comp = (s - sum) - y;
+                sum = s;
+                t[k] = split_ld(sum - comp);
+            }
+            HX_TRY(upload_vec(lf, t));
+        }
+        HX_TRY(upload_vec(psi, phase_table(lmax, ps)));
+        HX_TRY(upload_vec(phi, phase_table(lmax, ph)));
+        P.lmax = lmax;
+        // cos(theta) = xh + xl with xh a multiple of 2^-22: l(l+1) xh - m m' (below 2^31) is then exact in the kernel's inner fma and
+        // the outer one rounds l(l+1) x - m m' once.  With xh the nearest double the inner fma rounded away what xl was to add wherever
+        // the two terms do not cancel: cos(theta) was a double in effect, theta off by up to 1.1e-16 / tan(theta), times lmax in d^l
+        const long double cx = cosl(th);
+        const double2 lc = split_ld(log2l(cosl(th / 2))), ls = split_ld(log2l(sinl(th / 2)));
+        P.xh = (double)ldexpl(rintl(ldexpl(cx, 22)), -22);
+        P.xl = (double)(cx - (long double)P.xh);
+        P.lc = DD{lc.x, lc.y};
+        P.ls = DD{ls.x, ls.y};
+        P.lf = (share ? share->lf : lf).as<double2>();
+        P.ppsi = psi.as<double2>();
+        P.pphi = phi.as<double2>();
+        return HX_OK;
+    }
+
+    void launch(int ncomp, const double2 *in, double2 *out, hipStream_t st) const
+    {
+        const dim3 grid((unsigned)((P.lmax + 1 + ROT_MO - 1) / ROT_MO), (unsigned)((ncomp + ROT_CB - 1) / ROT_CB));
+        hipLaunchKernelGGL(k_rotate_alm, grid, dim3(ROT_MO * ROT_MB), 0, st, P, ncomp, in, out);
+    }
+};
+
 }  // namespace
 
 int rotate_exec_flops(unsigned long long *v, bool reset)
@@ -274,14 +331,16 @@ extern "C" int hx_rotate_alm(int lmax, int ncomp, const double _Complex *alm_in,
         if (a < b + bytes && b < a + bytes)
             return fail(HX_ERR_ARG, "hx_rotate_alm: alm_in and alm_out overlap (every output order needs every input order: there is no in-place rotation)");
     }
-    // theta into [0, pi]: Ry(-theta) = Rz(pi) Ry(theta) Rz(-pi)
-    long double th = fmodl((long double)theta, 2 * PI_L), ps = psi, ph = phi;
-    if (th < 0) th += 2 * PI_L;
-    if (th > PI_L) {
-        th = 2 * PI_L - th;
+    // theta into [0, pi] through its half angle: cosl and sinl reduce any argument exactly (theta mod a 64-bit 2 pi is off by 3e-19 per
+    // turn, times lmax in the phase of d), theta and theta + 2 pi give the same d^l, and cos(theta/2) sin(theta/2) < 0 is a theta in
+    // (pi, 2 pi): Ry(-theta) = Rz(pi) Ry(theta) Rz(-pi)
+    long double ps = psi, ph = phi;
+    const long double hc = cosl((long double)theta / 2), hs = sinl((long double)theta / 2);
+    if ((hc < 0) != (hs < 0) && hc != 0 && hs != 0) {
         ps -= PI_L;
         ph += PI_L;
     }
+    const long double th = 2 * atan2l(fabsl(hs), fabsl(hc));
     ps = fmodl(ps, 2 * PI_L);
     ph = fmodl(ph, 2 * PI_L);
     const bool at_zero = th == 0, at_pi = (double)th == (double)PI_L;
@@ -291,39 +350,27 @@ extern "C" int hx_rotate_alm(int lmax, int ncomp, const double _Complex *alm_in,
     OutView vout;
     HX_TRY(vout.bind(alm_out, bytes));
     hipStream_t st = rt().stream;
-    DevBuf b_psi, b_phi, b_lf;
+    DevBuf b_phi, b_mid;
+    RotTables t1, t2;
     if (at_zero || at_pi) {
         // a'_lm = exp(-i m (phi + psi)) a_lm;  at pi: (-1)^l exp(-i m (phi - psi)) conj(a_lm)
         HX_TRY(upload_vec(b_phi, phase_table(lmax, at_zero ? ph + ps : ph - ps)));
         ProfScope prof("rotate_alm");
         hipLaunchKernelGGL(k_rotate_phase, dim3((unsigned)((nl + 255) / 256), (unsigned)nl, (unsigned)ncomp), dim3(256), 0, st, lmax, at_pi ? 1 : 0,
                            b_phi.as<double2>(), vin.as<double2>(), vout.as<double2>());
-    } else {
-        std::vector<double2> lf(2 * nl);
-        long double sum = 0, comp = 0;  // log2 k!, compensated
-        lf[0] = make_double2(0.0, 0.0);
-        for (size_t k = 1; k < lf.size(); ++k) {
-            const long double y = log2l((long double)k) - comp, t = sum + y;
-            comp = (t - sum) - y;
-            sum = t;
-            lf[k] = split_ld(sum - comp);
-        }
-        HX_TRY(upload_vec(b_lf, lf));
-        HX_TRY(upload_vec(b_psi, phase_table(lmax, ps)));
-        HX_TRY(upload_vec(b_phi, phase_table(lmax, ph)));
-        RotParams P;
-        P.lmax = lmax;
-        const double2 x = split_ld(cosl(th)), lc = split_ld(log2l(cosl(th / 2))), ls = split_ld(log2l(sinl(th / 2)));
-        P.xh = x.x;
-        P.xl = x.y;
-        P.lc = DD{lc.x, lc.y};
-        P.ls = DD{ls.x, ls.y};
-        P.lf = b_lf.as<double2>();
-        P.ppsi = b_psi.as<double2>();
-        P.pphi = b_phi.as<double2>();
+    } else if (sinl(th) < ROT_SPLIT_SIN) {
+        // d^l(theta) = d^l(pi/2) d^l(theta - pi/2): two rotations by angles of order one through a scratch alm, since the FP64 chains
+        // lose 1 / sin(theta).  theta - pi/2 stays a long double: rounded to a double it is lmax 1e-16 of phase
+        HX_TRY(b_mid.alloc(bytes));
+        HX_TRY(t1.build(lmax, ps, PI_L / 2, 0));
+        HX_TRY(t2.build(lmax, 0, th - PI_L / 2, ph, &t1));
         ProfScope prof("rotate_alm");
-        const dim3 grid((unsigned)((nl + ROT_MO - 1) / ROT_MO), (unsigned)((ncomp + ROT_CB - 1) / ROT_CB));
-        hipLaunchKernelGGL(k_rotate_alm, grid, dim3(ROT_MO * ROT_MB), 0, st, P, ncomp, vin.as<double2>(), vout.as<double2>());
+        t1.launch(ncomp, vin.as<double2>(), b_mid.as<double2>(), st);
+        t2.launch(ncomp, b_mid.as<double2>(), vout.as<double2>(), st);
+    } else {
+        HX_TRY(t1.build(lmax, ps, th, ph));
+        ProfScope prof("rotate_alm");
+        t1.launch(ncomp, vin.as<double2>(), vout.as<double2>(), st);
     }
     HX_HIP(hipGetLastError());
     HX_TRY(vout.finish());

@@ -588,7 +588,9 @@ int hx_jk_regions(int nside, const double *weight, int njk, int32_t *labels, dou
  * imaginary part of a_l0 is not read and comes back as exactly 0.  alm_in, alm_out: (ncomp, nlm) complex128 in the layout of every alm
  * here (m-major, mmax = lmax); every component is rotated with the same matrices (E and B of a field of any spin weight rotate as
  * scalars).  Any finite angles: theta is brought into [0, pi] on the host ((psi, theta, phi) -> (psi - pi, -theta, phi + pi)),
- * theta = 0 and theta = pi take their closed forms.  The sum over m' has a fixed order: the result is bit-identical from call to call
+ * theta = 0 and theta = pi take their closed forms; below sin(theta) = 0.1 the rotation is done as two, by pi/2 and theta - pi/2,
+ * through a scratch alm of the size of the input (the FP64 recurrence loses 1 / sin(theta): DESIGN.md 4.18), at twice the time.
+ * 1e-12 of max |a| holds for every angle up to lmax 6144 at least.  The sum over m' has a fixed order: the result is bit-identical from call to call
  * and does not depend on how the components are batched.
  * Host or device pointers, as everywhere in this header.  The two arrays must not overlap (every output order needs every input
  * order): HX_ERR_ARG, as are lmax < 0, ncomp < 1 and an angle that is NaN or Inf; lmax > 32000 is HX_ERR_UNSUPPORTED.  Runs on the

@@ -1,5 +1,5 @@
 """hx_rotate_alm at production size: alms resident in HBM, lmax 2048 and 6144 (env LMAXS), 1 and 8 components (env NCOMPS), generic
-angles.
+angles (env ANGLES: psi,theta,phi).
 
 Per case: the whole call (host tables in long doubles, their upload, the kernel) by the library's event timer (hx_timer_*), and the
 rotation kernel alone from the library's `rotate_alm` scope in calls of their own; each warmed up, median and min .. max of REPS.  The
@@ -25,7 +25,7 @@ LMAXS = [int(x) for x in os.environ.get("LMAXS", "2048,6144").split(",")]
 NCOMPS = [int(x) for x in os.environ.get("NCOMPS", "1,8").split(",")]
 REPS = int(os.environ.get("REPS", "5"))
 OUT = os.environ.get("OUT", "profiles/rotate_alm.json")
-ANGLES = (0.7, 1.234, -2.1)
+ANGLES = tuple(float(x) for x in os.environ.get("ANGLES", "0.7,1.234,-2.1").split(","))  # sin(theta) < 0.1: the two-pass path
 
 
 def summary(xs):
@@ -68,7 +68,7 @@ def main():
             # the pair of chains (m, |m'|) advances lmax - max(m, |m'|) steps; every block of TILE_COMP components runs them again
             d = lmax - np.arange(lmax + 1, dtype=np.float64)  # lmax - m: m + 1 pairs with |m'| <= m, then lmax - |m'| for the others
             pair_steps = float(((lmax + 1 - d) * d + d * (d - 1) / 2).sum()) * -(-n // TILE_COMP)
-            row = {"lmax": lmax, "ncomp": n, "call": summary(whole), "kernel": summary(kernel), "pair_steps": pair_steps,
+            row = {"lmax": lmax, "ncomp": n, "angles": ANGLES, "call": summary(whole), "kernel": summary(kernel), "pair_steps": pair_steps,
                    "executed_gflop": flops / 1e9, "gflops": flops / k / 1e6, "fp64_valu_share": flops / k / 1e9 / peaks["fp64_valu_tflops"],
                    "ns_per_pair_step": k * 1e6 / pair_steps}
             rows.append(row)
