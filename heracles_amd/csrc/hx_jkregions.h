@@ -1,41 +1,31 @@
 // hx_jkregions.h -- the definition of the equal-weight sky segmentation as pure functions: the integer pixel
-// weights, the order-preserving key of a projection, the weight target and the clamped count of a split, the unit vector of a RING
-// pixel centre, and the principal axis of a 3 x 3 covariance with its sign rule.  Usable from device code and from the host test
-// (tests/csrc/test_jkregions.cpp), which runs the very code hx_jkregions.hip runs.  Compiles with plain g++.
+// weights, the order-preserving key of a projection, the weight target and the clamped count of a split, and the principal axis of a
+// 3 x 3 covariance with its sign rule; the unit vector of a pixel centre, pix2vec_ring, is that of hx_healpix.h.  Usable from device
+// code and from the host test (tests/csrc/test_jkregions.cpp), which runs the very code hx_jkregions.hip runs.  Compiles with plain g++.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hx_mockcat.h"  // isqrt_ll, div32: the ring arithmetic of ring2xyf
-
-#if defined(__HIPCC__)
-#define HX_JK_HD __host__ __device__ inline
-#else
-#define HX_JK_HD inline
-#endif
-
-#if defined(__clang__)
-#define HX_JK_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define HX_JK_NO_CONTRACT
-#endif
+#include "hx_healpix.h"  // HX_PIX_HD, HX_PIX_NO_CONTRACT, pix2vec_ring
 
 namespace hxjk {
+
+using hxpix::pix2vec_ring;  // unit vector of the centre of a RING pixel
 
 constexpr int NJK_MAX = 4096;
 constexpr int NMOM = 10;  // S0, S1 (x, y, z), S2 (xx, xy, xz, yy, yz, zz)
 
-HX_JK_HD bool weight_valid(double w) { return w >= 0.0 && w <= 1.7976931348623157e308; }  // (a NaN fails both)
+HX_PIX_HD bool weight_valid(double w) { return w >= 0.0 && w <= 1.7976931348623157e308; }  // (a NaN fails both)
 
 // q = max(1, llrint(w / wmax 2^32)) for 0 < w <= wmax: every later weight sum is an exact 64-bit integer
-HX_JK_HD uint64_t quantise(double w, double wmax)
+HX_PIX_HD uint64_t quantise(double w, double wmax)
 {
     const long long r = llrint(w / wmax * 4294967296.0);
     return r < 1 ? 1ull : (uint64_t)r;
 }
 
 // order-preserving double -> 64-bit key of t + 0.0 (which maps -0 to +0): a < b  <=>  key(a) < key(b)
-HX_JK_HD uint64_t order_key(double t)
+HX_PIX_HD uint64_t order_key(double t)
 {
     const double u = t + 0.0;
     uint64_t b;
@@ -44,7 +34,7 @@ HX_JK_HD uint64_t order_key(double t)
 }
 
 // T = floor(Q n1 / n) for Q < 2^63 and 0 < n1 < n <= 4096: long division in base 2^32, no 128-bit type
-HX_JK_HD uint64_t split_target(uint64_t Q, uint32_t n1, uint32_t n)
+HX_PIX_HD uint64_t split_target(uint64_t Q, uint32_t n1, uint32_t n)
 {
     uint64_t a = (Q >> 32) * n1, b = (Q & 0xffffffffull) * n1;  // Q n1 = a 2^32 + b
     a += b >> 32;
@@ -55,58 +45,26 @@ HX_JK_HD uint64_t split_target(uint64_t Q, uint32_t n1, uint32_t n)
 }
 
 // does the pixel with exclusive prefix E and weight q go left of the target T?  2 E + q <= 2 T
-HX_JK_HD bool goes_left(uint64_t E, uint64_t q, uint64_t T) { return 2ull * E + q <= 2ull * T; }
+HX_PIX_HD bool goes_left(uint64_t E, uint64_t q, uint64_t T) { return 2ull * E + q <= 2ull * T; }
 
 // the count of left pixels clamped to [n1, m - (n - n1)]: no region is left without a pixel (m >= n)
-HX_JK_HD uint32_t clamp_count(uint32_t c, uint32_t m, uint32_t n1, uint32_t n)
+HX_PIX_HD uint32_t clamp_count(uint32_t c, uint32_t m, uint32_t n1, uint32_t n)
 {
     const uint32_t lo = n1, hi = m - (n - n1);
     return c < lo ? lo : (c > hi ? hi : c);
 }
 
-// unit vector of the centre of RING pixel pix, any nside in 1 .. 8192 (pix2ang of the HEALPix paper; sin(theta) of the cap rings from
-// 1 - |z| directly).  The ring and the index in it as hxmock::ring2xyf finds them; a centre needs no face coordinates.
-HX_JK_HD void pix2vec_ring(long long nside, long long pix, double *x, double *y, double *z)
-{
-    HX_JK_NO_CONTRACT
-    const long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1), nl4 = 4 * nside;
-    const double fact2 = 4.0 / (double)npix, halfpi = 1.57079632679489661923;
-    double zz, sth, phi;
-    if (pix < ncap) {
-        const long long iring = (1 + hxmock::isqrt_ll(1 + 2 * pix)) >> 1, iphi = (pix + 1) - 2 * iring * (iring - 1);
-        const double t = (double)(iring * iring) * fact2;
-        zz = 1.0 - t;
-        sth = sqrt(t * (2.0 - t));
-        phi = ((double)iphi - 0.5) * halfpi / (double)iring;
-    } else if (pix < npix - ncap) {
-        const long long ip = pix - ncap, tmp = hxmock::div32(ip, nl4), iring = tmp + nside, iphi = ip - tmp * nl4 + 1;
-        const double fodd = ((iring + nside) & 1) ? 1.0 : 0.5;
-        zz = (double)(2 * nside - iring) * (2.0 / (3.0 * (double)nside));
-        sth = sqrt((1.0 - zz) * (1.0 + zz));
-        phi = ((double)iphi - fodd) * halfpi / (double)nside;
-    } else {
-        const long long ip = npix - pix, iring = (1 + hxmock::isqrt_ll(2 * ip - 1)) >> 1, iphi = 4 * iring + 1 - (ip - 2 * iring * (iring - 1));
-        const double t = (double)(iring * iring) * fact2;
-        zz = t - 1.0;
-        sth = sqrt(t * (2.0 - t));
-        phi = ((double)iphi - 0.5) * halfpi / (double)iring;
-    }
-    *x = sth * cos(phi);
-    *y = sth * sin(phi);
-    *z = zz;
-}
-
 // t = a . v, summed x, y, z in that order without fused multiply-adds
-HX_JK_HD double project(const double a[3], double x, double y, double z)
+HX_PIX_HD double project(const double a[3], double x, double y, double z)
 {
-    HX_JK_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     return (a[0] * x + a[1] * y) + a[2] * z;
 }
 
 // C (xx, xy, xz, yy, yz, zz) = S2 / S0 - (S1 / S0)(S1 / S0)^T from the ten moments
-HX_JK_HD void covariance(const double mom[NMOM], double C[6])
+HX_PIX_HD void covariance(const double mom[NMOM], double C[6])
 {
-    HX_JK_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     const double s0 = mom[0], mx = mom[1] / s0, my = mom[2] / s0, mz = mom[3] / s0;
     C[0] = mom[4] / s0 - mx * mx;
     C[1] = mom[5] / s0 - mx * my;
@@ -121,9 +79,9 @@ HX_JK_HD void covariance(const double mom[NMOM], double C[6])
 // y = adj(C - lambda I) a: the adjugate of the (numerically singular) shifted matrix is its inverse without the common factor
 // 1 / det, so the step needs no division and cannot overflow; it brings the error of a down to rounding / (relative gap).  With two
 // (nearly) equal leading eigenvalues the axis is whatever the sweeps leave.
-HX_JK_HD void principal_axis(const double C[6], double a[3])
+HX_PIX_HD void principal_axis(const double C[6], double a[3])
 {
-    HX_JK_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     double scale = 0.0;
     for (int k = 0; k < 6; ++k) scale = fabs(C[k]) > scale ? fabs(C[k]) : scale;
     if (!(scale > 0.0)) {

@@ -1,133 +1,53 @@
-// hx_masktools.h -- the definition of the mask tools as pure functions: the geometry of a HEALPix ring, the chord
-// measure h = 1 - cos(angle) between two unit vectors, the rings and the conservative phi window of a disc, the per-ring neighbour
-// tables of a mask and the pruned search for the nearest masked pixel over them, and the C1 / C2 tapers.  Usable from device code and
-// from the host test (tests/csrc/test_masktools.cpp), which runs the very code hx_masktools.hip runs.  Compiles with plain g++.
+// hx_masktools.h -- the definition of the mask tools as pure functions: the chord measure
+// h = 1 - cos(angle) between two unit vectors, the rings and the conservative phi window of a disc, the per-ring neighbour tables of a
+// mask and the pruned search for the nearest masked pixel over them, and the C1 / C2 tapers, all on the ring geometry of hx_healpix.h
+// (Ring).  Usable from device code and from the host test (tests/csrc/test_masktools.cpp), which runs the very code
+// hx_masktools.hip runs.  Compiles with plain g++.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hx_jkregions.h"  // pix2vec_ring: the centre of a pixel
+#include "hx_healpix.h"  // the geometry of a ring and of its pixel centres
 
-#define HX_MT_HD HX_JK_HD
-#define HX_MT_NO_CONTRACT HX_JK_NO_CONTRACT
+// tests/csrc/test_masktools.cpp includes this header alone and compares ring_vec with the pixel centre under the name hx_jkregions.h
+// gives it; repeated here so that the mask tools need not include the jackknife header for it
+namespace hxjk {
+using hxpix::pix2vec_ring;
+}
 
 namespace hxmask {
 
+using hxpix::HALFPI;
+using hxpix::Ring;
+using hxpix::pix2ring;
+using hxpix::ring_above;
+using hxpix::ring_index_of_phi;
+using hxpix::ring_info;
+using hxpix::ring_phi;
+using hxpix::ring_vec;
+
 constexpr uint32_t NONE = 0xffffffffu;  // "no masked pixel" in the neighbour tables
-constexpr double DEG = 0.017453292519943295, HALFPI = 1.57079632679489661923, PI = 3.14159265358979323846, TWOPI = 6.28318530717958647692;
+constexpr double DEG = 0.017453292519943295, PI = 3.14159265358979323846, TWOPI = 6.28318530717958647692;
 constexpr int KIND_C1 = 1, KIND_C2 = 2;
 constexpr double WIDE_MIN = 512.0;  // discs with more pixels than this (estimated) get a work-group of their own
 
-HX_MT_HD bool finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }  // (a NaN fails both)
-HX_MT_HD bool is_masked(double m) { return m <= 0.0; }
+HX_PIX_HD bool finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }  // (a NaN fails both)
+HX_PIX_HD bool is_masked(double m) { return m <= 0.0; }
 
 // h(u, v) = 1 - cos(angle between u and v) in the chord form, summed x, y, z in that order
-HX_MT_HD double chord_h(double ux, double uy, double uz, double vx, double vy, double vz)
+HX_PIX_HD double chord_h(double ux, double uy, double uz, double vx, double vy, double vz)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     const double dx = ux - vx, dy = uy - vy, dz = uz - vz;
     return 0.5 * ((dx * dx + dy * dy) + dz * dz);
 }
 
 // h of an angle in degrees: 2 sin^2(angle / 2)
-HX_MT_HD double angle_h(double deg)
+HX_PIX_HD double angle_h(double deg)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     const double s = sin(0.5 * (deg * DEG));
     return 2.0 * s * s;
-}
-
-// ---- ring geometry: ring ir in 1 .. 4 nside - 1, its pixels j in 0 .. n - 1 at phi = (j + 1 - shift) (pi / 2) / div ----
-struct Ring {
-    long long first, n;  // first RING pixel, number of pixels
-    double z, sth, shift, div;
-};
-
-// the expressions of hxjk::pix2vec_ring, per ring: ring_vec(ring_info(nside, ir), j) has the bits of pix2vec_ring(nside, first + j)
-HX_MT_HD Ring ring_info(long long nside, long long ir)
-{
-    HX_MT_NO_CONTRACT
-    const long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1);
-    const double fact2 = 4.0 / (double)npix;
-    Ring r;
-    if (ir < nside) {
-        const double t = (double)(ir * ir) * fact2;
-        r.first = 2 * ir * (ir - 1);
-        r.n = 4 * ir;
-        r.z = 1.0 - t;
-        r.sth = sqrt(t * (2.0 - t));
-        r.shift = 0.5;
-        r.div = (double)ir;
-    } else if (ir <= 3 * nside) {
-        const double zz = (double)(2 * nside - ir) * (2.0 / (3.0 * (double)nside));
-        r.first = ncap + (ir - nside) * 4 * nside;
-        r.n = 4 * nside;
-        r.z = zz;
-        r.sth = sqrt((1.0 - zz) * (1.0 + zz));
-        r.shift = ((ir + nside) & 1) ? 1.0 : 0.5;
-        r.div = (double)nside;
-    } else {
-        const long long irs = 4 * nside - ir;
-        const double t = (double)(irs * irs) * fact2;
-        r.first = npix - 2 * irs * (irs + 1);
-        r.n = 4 * irs;
-        r.z = t - 1.0;
-        r.sth = sqrt(t * (2.0 - t));
-        r.shift = 0.5;
-        r.div = (double)irs;
-    }
-    return r;
-}
-
-HX_MT_HD double ring_phi(const Ring &r, long long j)
-{
-    HX_MT_NO_CONTRACT
-    return ((double)(j + 1) - r.shift) * HALFPI / r.div;
-}
-
-HX_MT_HD void ring_vec(const Ring &r, long long j, double *x, double *y, double *z)
-{
-    HX_MT_NO_CONTRACT
-    const double phi = ring_phi(r, j);
-    *x = r.sth * cos(phi);
-    *y = r.sth * sin(phi);
-    *z = r.z;
-}
-
-// the (fractional) in-ring index at which the ring reaches phi: pixel j sits at j
-HX_MT_HD double ring_index_of_phi(const Ring &r, double phi)
-{
-    HX_MT_NO_CONTRACT
-    return phi * (r.div / HALFPI) - (1.0 - r.shift);
-}
-
-// RING pixel -> (ring 1 .. 4 nside - 1, index in the ring), the branches of pix2vec_ring
-HX_MT_HD void pix2ring(long long nside, long long pix, long long *ir, long long *j)
-{
-    const long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1), nl4 = 4 * nside;
-    if (pix < ncap) {
-        const long long iring = (1 + hxmock::isqrt_ll(1 + 2 * pix)) >> 1;
-        *ir = iring;
-        *j = pix - 2 * iring * (iring - 1);
-    } else if (pix < npix - ncap) {
-        const long long ip = pix - ncap, tmp = hxmock::div32(ip, nl4);
-        *ir = tmp + nside;
-        *j = ip - tmp * nl4;
-    } else {
-        const long long ip = npix - pix, irs = (1 + hxmock::isqrt_ll(2 * ip - 1)) >> 1;
-        *ir = nl4 - irs;
-        *j = 4 * irs - (ip - 2 * irs * (irs - 1));
-    }
-}
-
-// the ring at or just above z (0 above the first ring), healpix's ring_above for any nside
-HX_MT_HD long long ring_above(long long nside, double z)
-{
-    HX_MT_NO_CONTRACT
-    const double az = fabs(z);
-    if (az <= 2.0 / 3.0) return (long long)((double)nside * (2.0 - 1.5 * z));
-    const long long ir = (long long)((double)nside * sqrt(3.0 * (1.0 - az)));
-    return z > 0.0 ? ir : 4 * nside - ir - 1;
 }
 
 // ---- discs ----
@@ -137,14 +57,14 @@ struct Disc {
     double theta, rad, hr;  // colatitude and radius in radians, h(radius)
 };
 
-HX_MT_HD bool disc_valid(double lon, double lat, double radius)
+HX_PIX_HD bool disc_valid(double lon, double lat, double radius)
 {
     return finite(lon) && lat >= -90.0 && lat <= 90.0 && radius >= 0.0 && radius <= 180.0;  // (a NaN fails)
 }
 
-HX_MT_HD Disc make_disc(double lon, double lat, double radius)
+HX_PIX_HD Disc make_disc(double lon, double lat, double radius)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     const double lo = lon * DEG, la = lat * DEG;
     Disc d;
     d.s = cos(la);
@@ -160,12 +80,12 @@ HX_MT_HD Disc make_disc(double lon, double lat, double radius)
 }
 
 // an estimate of the number of pixel centres in the disc: the area of the cap in pixels
-HX_MT_HD double disc_pixels(long long nside, double hr) { return 6.0 * (double)nside * (double)nside * hr; }
+HX_PIX_HD double disc_pixels(long long nside, double hr) { return 6.0 * (double)nside * (double)nside * hr; }
 
-HX_MT_HD bool disc_has_pole(const Disc &d) { return d.theta - d.rad <= 0.0 || d.theta + d.rad >= PI; }
+HX_PIX_HD bool disc_has_pole(const Disc &d) { return d.theta - d.rad <= 0.0 || d.theta + d.rad >= PI; }
 
 // the rings whose colatitude lies within the radius of the centre's, widened by a ring or two: lo .. hi inclusive
-HX_MT_HD void disc_rings(long long nside, const Disc &d, long long *lo, long long *hi)
+HX_PIX_HD void disc_rings(long long nside, const Disc &d, long long *lo, long long *hi)
 {
     const double tlo = d.theta - d.rad, thi = d.theta + d.rad;
     const double zhi = tlo <= 0.0 ? 1.0 : cos(tlo), zlo = thi >= PI ? -1.0 : cos(thi);
@@ -186,9 +106,9 @@ struct Window {
     long long k0, count;
 };
 
-HX_MT_HD Window disc_window(const Ring &r, const Disc &d)
+HX_PIX_HD Window disc_window(const Ring &r, const Disc &d)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     Window w = {0, r.n};
     if (disc_has_pole(d)) return w;
     const double ss = r.sth * d.s;
@@ -206,14 +126,14 @@ HX_MT_HD Window disc_window(const Ring &r, const Disc &d)
     return w;
 }
 
-HX_MT_HD long long wrap_index(long long k, long long n)
+HX_PIX_HD long long wrap_index(long long k, long long n)
 {
     const long long j = k % n;
     return j < 0 ? j + n : j;
 }
 
 // the rule: is the centre of pixel j of ring r inside the disc?
-HX_MT_HD bool disc_hit(const Ring &r, long long j, const Disc &d)
+HX_PIX_HD bool disc_hit(const Ring &r, long long j, const Disc &d)
 {
     double x, y, z;
     ring_vec(r, j, &x, &y, &z);
@@ -224,7 +144,7 @@ HX_MT_HD bool disc_hit(const Ring &r, long long j, const Disc &d)
 // left[p]: the in-ring index of the nearest masked pixel at or before p on p's ring, right[p]: at or after p (NONE: there is none on
 // that side); first / last [ring]: the first and the last masked index of the ring (NONE: the ring has no masked pixel), for the
 // wrap-around.  One ring, in order (the device builds the same tables with a scan per ring):
-HX_MT_HD void ring_neighbours(const double *mask, const Ring &r, uint32_t *left, uint32_t *right, uint32_t *first, uint32_t *last)
+HX_PIX_HD void ring_neighbours(const double *mask, const Ring &r, uint32_t *left, uint32_t *right, uint32_t *first, uint32_t *last)
 {
     uint32_t seen = NONE;
     *first = NONE;
@@ -253,9 +173,9 @@ struct Neighbours {
 // (h to a fixed point is monotone in |dphi| on either side), each with its wrap-around; a direction stops at the first ring whose
 // lower bound -- the chord between the two colatitudes, monotone in the ring offset -- reaches the best value so far (which starts
 // at the cap).  evals, unless null, counts the evaluations of h.
-HX_MT_HD double nearest_h(long long nside, long long pix, double cap, const Neighbours &nb, unsigned long long *evals)
+HX_PIX_HD double nearest_h(long long nside, long long pix, double cap, const Neighbours &nb, unsigned long long *evals)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     long long ir0, j0;
     pix2ring(nside, pix, &ir0, &j0);
     const Ring r0 = ring_info(nside, ir0);
@@ -293,16 +213,16 @@ HX_MT_HD double nearest_h(long long nside, long long pix, double cap, const Neig
 }
 
 // ---- tapers: w(x) on x = sqrt(H / h(aposize)) in [0, 1], w(0) = 0, w(1) = 1 ----
-HX_MT_HD bool kind_valid(int kind) { return kind == KIND_C1 || kind == KIND_C2; }
+HX_PIX_HD bool kind_valid(int kind) { return kind == KIND_C1 || kind == KIND_C2; }
 
-HX_MT_HD double taper(int kind, double x)
+HX_PIX_HD double taper(int kind, double x)
 {
-    HX_MT_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     if (x >= 1.0) return 1.0;
     if (!(x > 0.0)) return 0.0;
     return kind == KIND_C1 ? x - sin(TWOPI * x) / TWOPI : 0.5 * (1.0 - cos(PI * x));
 }
 
-HX_MT_HD double taper_of_h(int kind, double H, double hcap) { return taper(kind, sqrt(H / hcap)); }
+HX_PIX_HD double taper_of_h(int kind, double H, double hcap) { return taper(kind, sqrt(H / hcap)); }
 
 }  // namespace hxmask

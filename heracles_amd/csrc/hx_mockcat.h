@@ -1,23 +1,21 @@
 // hx_mockcat.h -- the definition of a Poisson-sampled mock catalogue as pure functions: the two Poisson samplers,
-// RING pixel -> (face, ix, iy), and (face, ix, iy, u, v) -> (lon, lat).  Usable from device code and from the host test
-// (tests/csrc/test_mockcat.cpp), which runs the very code the kernels of hx_mockcat.hip run.
+// the sub-pixel offsets and the position of a point (through the face coordinates of hx_healpix.h), and the noise of a value.  Usable
+// from device code and from the host test (tests/csrc/test_mockcat.cpp), which runs the very code the kernels of hx_mockcat.hip run.
 //
 // Random bits: Philox4x32-10 (hx_philox.h), key (seed & 0xffffffff, seed >> 32), counter (RING pixel, index, 0x80000000 | stream,
 // realisation).  Stream 0: the count draws of the pixel (index 0 the inversion uniform, index = iteration of the rejection sampler);
 // stream 1: the position of the index-th point of the pixel; stream 2 + j: the noise of value column j of that point.
 //
 // Every function rounds operation by operation (no contraction into fused multiply-adds), so that the host and the device differ only
-// where their exp / log / lgamma / sqrt / atan2 do.
+// where their exp / log / lgamma / sqrt do, and in the positions the sqrt / atan2 of hxpix::xyf2lonlat.
 #pragma once
+#include "hx_healpix.h"
 #include "hx_philox.h"
 
-#if defined(__clang__)
-#define HX_MOCK_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define HX_MOCK_NO_CONTRACT
-#endif
-
 namespace hxmock {
+
+using hxpix::ring2xyf;    // RING pixel -> (face, ix, iy)
+using hxpix::xyf2lonlat;  // (face, ix, iy, u, v) -> (lon, lat)
 
 constexpr uint32_t STREAM_BIT = 0x80000000u;  // third counter word: disjoint from hx_synalm's components (< 64)
 constexpr uint32_t STREAM_COUNT = 0, STREAM_POSITION = 1, STREAM_VALUE0 = 2;
@@ -31,7 +29,7 @@ HX_PHILOX_HD bool lambda_valid(double lam) { return lam >= 0.0 && lam <= LAMBDA_
 // Inversion by sequential search, 0 < lam < 32, on the uniform u in [0, 1).
 HX_PHILOX_HD long long poisson_inversion(double lam, double u)
 {
-    HX_MOCK_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     double p = exp(-lam), cdf = p;
     int k = 0;
     while (u >= cdf && k < INVERSION_KMAX) {
@@ -45,7 +43,7 @@ HX_PHILOX_HD long long poisson_inversion(double lam, double u)
 // Hoermann's PTRS (transformed rejection with squeeze, 1993), 32 <= lam <= 2^30; (u1, u2) of one Philox call per iteration.
 HX_PHILOX_HD long long poisson_ptrs(double lam, uint32_t pixel, uint32_t realisation, uint32_t k0, uint32_t k1)
 {
-    HX_MOCK_NO_CONTRACT
+    HX_PIX_NO_CONTRACT
     const double slam = sqrt(lam), loglam = log(lam);
     const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
     const double inva = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
@@ -73,94 +71,11 @@ HX_PHILOX_HD long long poisson_count(double lam, uint32_t pixel, uint32_t realis
     return poisson_ptrs(lam, pixel, realisation, k0, k1);
 }
 
-HX_PHILOX_HD long long isqrt_ll(long long v)  // floor(sqrt(v)), v < 2^52
-{
-    long long r = (long long)sqrt((double)v);
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return r;
-}
-
-HX_PHILOX_HD int face_jrll(int face) { return 2 + (face >> 2); }
-HX_PHILOX_HD int face_jpll(int face) { return face < 4 ? 2 * face + 1 : (face < 8 ? 2 * (face - 4) : 2 * (face - 8) + 1); }
-
-// a / b for 0 <= a < 2^32, 0 < b < 2^32: every quotient of ring2xyf at nside <= 8192 (12 nside^2 < 2^30), where a 64-bit division
-// costs the point kernel several times as much
-HX_PHILOX_HD long long div32(long long a, long long b) { return (long long)((uint32_t)a / (uint32_t)b); }
-
-// RING pixel -> (face, ix, iy), any nside in 1 .. 8192 (healpix_cxx ring2xyf without the power-of-two shifts).
-HX_PHILOX_HD void ring2xyf(long long nside, long long pix, int *face_out, long long *ix, long long *iy)
-{
-    const long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1), nl4 = 4 * nside;
-    long long iring, iphi, kshift, nr;
-    int face;
-    if (pix < ncap) {
-        iring = (1 + isqrt_ll(1 + 2 * pix)) >> 1;
-        iphi = (pix + 1) - 2 * iring * (iring - 1);
-        kshift = 0;
-        nr = iring;
-        face = (int)div32(iphi - 1, nr);
-    } else if (pix < npix - ncap) {
-        const long long ip = pix - ncap, tmp = div32(ip, nl4);
-        iring = tmp + nside;
-        iphi = ip - tmp * nl4 + 1;
-        kshift = (iring + nside) & 1;
-        nr = nside;
-        const long long ire = tmp + 1, irm = 2 * nside + 1 - tmp;
-        const long long ifm = div32(iphi - (ire >> 1) + nside - 1, nside), ifp = div32(iphi - (irm >> 1) + nside - 1, nside);
-        face = (int)((ifp == ifm) ? (ifp | 4) : ((ifp < ifm) ? ifp : (ifm + 8)));
-    } else {
-        const long long ip = npix - pix;
-        const long long ir = (1 + isqrt_ll(2 * ip - 1)) >> 1;
-        iphi = 4 * ir + 1 - (ip - 2 * ir * (ir - 1));
-        kshift = 0;
-        nr = ir;
-        iring = nl4 - ir;
-        face = (int)(8 + div32(iphi - 1, nr));
-    }
-    const long long irt = iring - face_jrll(face) * nside + 1;
-    long long ipt = 2 * iphi - face_jpll(face) * nr - kshift - 1;
-    if (ipt >= 2 * nside) ipt -= 8 * nside;
-    *face_out = face;
-    *ix = (ipt - irt) >> 1;
-    *iy = (-ipt - irt) >> 1;
-}
-
 // The sub-pixel offsets of one position call: ((x >> 8) + 1/2) 2^-24, strictly inside (0, 1) with a margin of 2^-25.
 HX_PHILOX_HD void offsets(const hxphilox::Words &w, double *u, double *v)
 {
     *u = ((double)(w.x[0] >> 8) + 0.5) * 0x1p-24;
     *v = ((double)(w.x[1] >> 8) + 0.5) * 0x1p-24;
-}
-
-// (face, ix, iy) and offsets (u, v) -> (lon, lat) in degrees: HEALPix's area-preserving face map (xyf2loc), lon in [0, 360).
-HX_PHILOX_HD void xyf2lonlat(long long nside, int face, long long ix, long long iy, double u, double v, double *lon, double *lat)
-{
-    HX_MOCK_NO_CONTRACT
-    const double x = ((double)ix + u) / (double)nside, y = ((double)iy + v) / (double)nside;
-    const double jr = ((double)face_jrll(face) - x) - y;
-    double nr, z, sth;
-    if (jr < 1.0) {
-        nr = jr;
-        const double t = nr * nr / 3.0;
-        z = 1.0 - t;
-        sth = sqrt(t * (2.0 - t));
-    } else if (jr > 3.0) {
-        nr = 4.0 - jr;
-        const double t = nr * nr / 3.0;
-        z = t - 1.0;
-        sth = sqrt(t * (2.0 - t));
-    } else {
-        nr = 1.0;
-        z = (2.0 - jr) * 2.0 / 3.0;
-        sth = sqrt((1.0 - z) * (1.0 + z));
-    }
-    double tmp = ((double)face_jpll(face) * nr + x) - y;
-    if (tmp < 0.0) tmp += 8.0;
-    if (tmp >= 8.0) tmp -= 8.0;
-    const double phi = 0.78539816339744830962 * tmp / nr;
-    *lon = phi * 57.295779513082320877;
-    *lat = atan2(z, sth) * 57.295779513082320877;
 }
 
 // The index-th point of RING pixel `pixel` (the counter word) at (face, ix, iy).
