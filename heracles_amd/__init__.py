@@ -67,6 +67,7 @@ from .twopoint import (
 )
 from .unmixing import naturalspice, naturalspice_batch
 from .weights import compute_pixel_weights
+from .pixwin import compute_pixel_window, find_window_file, read_pixel_window, write_pixel_window
 
 __all__ = [
     "HipHealpixMapper", "HipDiscreteMapper", "PointSHT", "PointField", "get_point_sht", "alm_resample", "Plan", "get_plan", "HxError", "init", "device_count", "synchronize",
@@ -77,7 +78,7 @@ __all__ = [
     "sample_covariance", "jackknife_covariance", "delete2_correction", "debias_covariance", "gaussian_covariance",
     "shrinkage_factor", "shrink", "flatten", "impose_correlation", "get_cl", "bias", "jackknife_bias",
     "map_catalogs", "catalog_alms", "ArrayCatalog", "FitsCatalog", "CatalogView", "FootprintFilter", "InvalidValueFilter", "Field", "Positions", "ScalarField", "ComplexField", "Spin2Field", "Shears", "Ellipticities",
-    "Visibility", "Weights", "get_masks", "compute_pixel_weights", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
+    "Visibility", "Weights", "get_masks", "compute_pixel_weights", "compute_pixel_window", "write_pixel_window", "read_pixel_window", "find_window_file", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
     "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
     "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
     "mask_discs", "mask_distance", "apodize_mask",

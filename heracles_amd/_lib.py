@@ -32,6 +32,7 @@ SYMBOLS = (
     "hx_pointsht_create", "hx_pointsht_destroy", "hx_pointsht_info", "hx_pointsht_adjoint",
     "hx_pointsht_synthesis", "hx_pointsht_grids", "hx_pointgrid_gather", "hx_pointgrid_destroy",
     "hx_pixel_weights_size", "hx_pixel_weights_expand", "hx_pixel_weights_solve",
+    "hx_pixel_window", "hx_pixel_window_rings",
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
     "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm", "hx_gauss_cov_accumulate",
@@ -165,6 +166,8 @@ def load():
         L.hx_pixel_weights_size.restype = C.c_int64
         L.hx_pixel_weights_expand.argtypes = [i, C.c_int64, dp, dp]
         L.hx_pixel_weights_solve.argtypes = [vp, i, C.c_double, i, dp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.hx_pixel_window.argtypes = [i, i, i, dp]
+        L.hx_pixel_window_rings.argtypes = [i, i, i, i, i, dp]
         L.hx_host_alloc.argtypes = [C.c_int64, C.POINTER(C.c_void_p)]
         L.hx_host_free.argtypes = [vp]
         L.hx_mixmat_gemm_clock.restype = C.c_double
@@ -291,10 +294,11 @@ def release_caches():
     0.31 GB each at lmax 6144 lie beside them), the Cholesky factor ``synalm`` keeps (23 MB at 30 components and lmax 6144), the folded
     coupling tables of ``gaussian_covariance_coupled`` ((spectra + 1) x bins x (lmax + 1) doubles: 0.22 GB at 465 spectra, 31 bins,
     lmax 2048), the partial tiles and the reduced matrix of ``deproject_templates`` (at most ~72 MB): hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
-    per result) go with them."""
-    from . import weights
+    per result) and the pixel windows ``compute_pixel_window`` keeps go with them."""
+    from . import pixwin, weights
 
     weights.release_computed()
+    pixwin.release_computed()
     check(load().hx_release_caches())
 
 

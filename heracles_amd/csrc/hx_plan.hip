@@ -350,7 +350,7 @@ int spin_data(hx_plan *pl, int spin, bool generic, hx_plan::SpinData **out)
 
 // libsharp's published heuristic for the largest m that contributes on a ring
 // (sharp_get_mlim): rings with m > mlim are skipped.
-static int ring_mlim(int lmax, int spin, double sth, double cth)
+int ring_mlim(int lmax, int spin, double sth, double cth)
 {
     double ofs = lmax * 0.01;
     if (ofs < 100.) ofs = 100.;

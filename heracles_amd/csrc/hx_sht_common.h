@@ -420,6 +420,7 @@ hx_plan *plan_create_equiangular(int N, int lmax);
 // per-spin state of a plan, built on first use.  generic: the run-time-spin family (1 <= spin <= lmax), else the kernels of spin 0 / spin 2
 int spin_data(hx_plan *pl, int spin, bool generic, hx_plan::SpinData **out);             // with its tables (filled on the library stream)
 int task_set(hx_plan *pl, int spin, bool generic, int blocks, hx_plan::TaskSet **out);   // tasks of `blocks` ring blocks each
+int ring_mlim(int lmax, int spin, double sth, double cth);                                // the largest order that contributes on a ring (the sweeps' threshold rule)
 int synth_mlim(hx_plan *pl, int spin, const int **mlim);                                 // SpinData::syn_mlim of the specialised family
 // hx_ring_fft.hip
 int ring_fft_plan_init(hx_plan *pl, const std::vector<int> &nsub, const std::vector<long long> &sN, const std::vector<long long> &sS);  // (hx_plan_create, behind the band-limit tables)

@@ -462,7 +462,7 @@ def read_vmap(filename, nside=None, field=0, *, transform=False, lmax=None, pixw
 
         nside_t = int(round((vmap.shape[0] / 12) ** 0.5))
         lmax_t = 3 * nside_t - 1 if lmax is None else int(lmax)
-        pw = pixel_window(nside_t, lmax_t, pixwin)[0]
+        pw = pixel_window(nside_t, lmax_t, pixwin, datapath if isinstance(pixwin, str) else None)[0]
         weights = load_pixel_weights(datapath, nside_t) if datapath is not None else None
         if datapath is not None and weights is None:
             raise FileNotFoundError(f"no pixel-weight file for NSIDE={nside_t} under datapath {datapath!r}")

@@ -9,7 +9,9 @@ Data healpy ships but this repository cannot (pixel-window tables, pixel-weight 
 is taken from the caller: pass ``pixwin=(pw_T, pw_P)`` / ``pixel_weights=...``; if they
 are omitted and the user's environment has healpy, its tables are used.  The pixel weights
 need no file: ``pixel_weights="compute"`` solves for them on the GPU on the first transform
-(heracles_amd/weights.py, ``compute_pixel_weights``).
+(heracles_amd/weights.py, ``compute_pixel_weights``).  Nor does the pixel window: ``pixwin="compute"`` computes it on the GPU
+from the pixel shapes, for any spin weight (heracles_amd/pixwin.py, ``compute_pixel_window``), so that the reference's default
+configuration (``deconvolve=True``) runs with no file and no healpy.
 """
 
 from __future__ import annotations
@@ -20,11 +22,29 @@ from . import sht
 from .core import DeviceArray, update_metadata
 
 
-def pixel_window(nside, lmax, pixwin=None):
-    """(pw_T, pw_P) up to lmax: explicit arrays, a callable(nside, lmax), or healpy's table."""
+def _computed_window(nside, lmax, spin, datapath=None):
+    """The window ``pixwin="compute"`` stands for: for spin 0 and 2 the table of a window file under ``datapath`` if there is one
+    (a user's healpy data directory is honoured), else the window computed on the GPU (heracles_amd/pixwin.py), which is kept."""
+    from .pixwin import compute_pixel_window, load_pixel_window
+
+    if spin in (0, 2) and datapath is not None:
+        pair = load_pixel_window(datapath, nside, lmax)
+        if pair is not None:
+            return pair[0 if spin == 0 else 1]
+    return compute_pixel_window(nside, lmax, spin)
+
+
+def pixel_window(nside, lmax, pixwin=None, datapath=None):
+    """(pw_T, pw_P) up to lmax: explicit arrays, a callable(nside, lmax), ``"compute"`` (the windows of spin 0 and 2 computed on
+    the GPU, or read from a window file under ``datapath``), or healpy's table."""
+    if isinstance(pixwin, str) and pixwin == "compute":
+        return _computed_window(nside, lmax, 0, datapath), _computed_window(nside, lmax, 2, datapath)
     if isinstance(pixwin, dict):
         # windows by spin weight: the pair of spin 0 and 2 if both are given, else healpy's table
         pixwin = (pixwin[0], pixwin[2]) if 0 in pixwin and 2 in pixwin else None
+        if pixwin is not None and any(isinstance(w, str) and w == "compute" for w in pixwin):
+            pixwin = tuple(_computed_window(nside, lmax, sp, datapath) if isinstance(w, str) and w == "compute" else w
+                           for w, sp in zip(pixwin, (0, 2)))
     if pixwin is not None:
         if callable(pixwin):
             pw0, pw2 = pixwin(nside, lmax)
@@ -244,12 +264,20 @@ class HipHealpixMapper:
 
     def _fl(self, spin):
         """1 / pixel window of the field's spin weight from l = |spin| on, or None without deconvolution.  healpy ships windows
-        for spin 0 and 2 only; a window of any weight may be given as ``pixwin={spin: array}``.  A weight without a window is
-        an error: the spin-2 window is never used in its place."""
+        for spin 0 and 2 only; a window of any weight may be given as ``pixwin={spin: array}``, or computed on the GPU for (nside,
+        lmax) on first use and kept: ``pixwin="compute"`` for every weight, ``pixwin={spin: "compute"}`` for one (a window file
+        under ``datapath`` is used for spin 0 and 2 if there is one).  A weight without a window is an error: the spin-2 window is
+        never used in its place."""
         if not self.__deconv:
             return None
-        if isinstance(self.pixwin, dict) and spin in self.pixwin:
-            pw = np.asarray(self.pixwin[spin], dtype=float)
+        path = self.datapath if self.datapath is not None else type(self).DATAPATH
+        if isinstance(self.pixwin, str) and self.pixwin == "compute":
+            pw = _computed_window(self.__nside, self.__lmax, spin, path)
+        elif isinstance(self.pixwin, dict) and spin in self.pixwin:
+            pw = self.pixwin[spin]
+            if isinstance(pw, str) and pw == "compute":
+                pw = _computed_window(self.__nside, self.__lmax, spin, path)
+            pw = np.asarray(pw, dtype=float)
             if pw.shape[-1] < self.__lmax + 1:
                 raise ValueError("pixel window shorter than lmax+1")
             pw = pw[: self.__lmax + 1]

@@ -524,6 +524,21 @@ int hx_pixel_weights_expand(int nside, int64_t ncompressed, const double *compre
 int hx_pixel_weights_solve(hx_plan *plan, int lmax, double epsilon, int itmax, double *compressed_out, int *iterations,
                            double *rel_gradient, double *max_residual);
 
+/* ---- HEALPix pixel window of any spin weight, computed from the pixel shapes (what healpy.pixwin reads from its data files) -----------
+ * A_lm(p) = the average of sY_lm over pixel p in the local (theta, phi) basis;
+ *     W_l^2 = 4 pi / ((2l+1) 12 nside^2) sum_p sum_{m=-l..l} |A_lm(p)|^2 for l >= spin, W_l = 1 for l < spin.
+ * Spin 0: the definition of the HEALPix primer (W_0 = 1).  Spin s != 0: the total-power window of the pixel-averaged field, one array
+ * for E and B (the E/B mixing of pixel averaging is not modelled).  Exact up to a 12-node Gauss-Legendre rule per half pixel in the
+ * one coordinate the integral does not close in; bit-identical from run to run.
+ * nside : 1 .. 8192, any integer;  spin : 0 .. lmax;  lmax : <= 4 nside (the rule is validated up to there) -- else HX_ERR_ARG
+ * hx_pixel_window       : window [lmax + 1], host or device
+ * hx_pixel_window_rings : for the northern rings ring_first .. ring_first + ring_count - 1 (1 = next to the pole, 2 nside = the equator)
+ *                         the ring's own sum (4 pi / (2l+1)) sum_{p in ring} sum_m |A_lm(p)|^2 (0 for l < spin): out [ring_count][lmax + 1],
+ *                         host or device.  The window is sqrt(sum_r c_r row_r / (12 nside^2)), added in ring order with c_r = 2 (the
+ *                         southern twin), 1 for the equator: hx_pixel_window forms exactly this sum.                                */
+int hx_pixel_window(int nside, int spin, int lmax, double *window);
+int hx_pixel_window_rings(int nside, int spin, int lmax, int ring_first, int ring_count, double *out);
+
 /* ---- covariance estimators of DICES (heracles/dices/jackknife.py:449-593, heracles/dices/shrinkage.py:66-98) ---------------------
  * Samples are stacked one per row in data-vector order; every array is row-major, host or device.  Columns are centred in two
  * passes, then every product runs on the FP64 matrix unit with K = the sample count; reductions in a fixed order (bitwise repeatable).
