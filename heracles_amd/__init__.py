@@ -40,7 +40,7 @@ from .fields import (
     Weights,
     get_masks,
 )
-from .masks import apodize_mask, mask_discs, mask_distance
+from .masks import apodize_mask, mask_discs, mask_distance, mask_polygons, rectangle_polygons
 from .deprojection import DeprojectionInfo, deproject_maps, deproject_templates, deprojection_bias
 from .mapping import catalog_alms, map_catalogs, transform
 from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
@@ -81,6 +81,6 @@ __all__ = [
     "Visibility", "Weights", "get_masks", "compute_pixel_weights", "compute_pixel_window", "write_pixel_window", "read_pixel_window", "find_window_file", "synalm", "synalm_components", "gaussian_maps", "poisson_catalog", "mock_catalogs",
     "jackknife_regions", "rotate_alm", "rotate_alms", "euler_from_matrix", "matrix_from_euler", "coord_matrix",
     "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
-    "mask_discs", "mask_distance", "apodize_mask",
+    "mask_discs", "mask_polygons", "rectangle_polygons", "mask_distance", "apodize_mask",
     "deproject_templates", "deproject_maps", "deprojection_bias", "DeprojectionInfo",
 ]

@@ -36,7 +36,7 @@ SYMBOLS = (
     "hx_ring_modes_size", "hx_ring_modes", "hx_legendre_from_modes", "hx_allgather_alms", "hx_host_alloc", "hx_host_free", "hx_mixmat_gemm_clock", "hx_mixmat_release", "hx_release_caches",
     "hx_cov_gram", "hx_cov_delete2", "hx_cov_shrink_sums",
     "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm", "hx_gauss_cov_accumulate",
-    "hx_mask_discs", "hx_mask_distance", "hx_mask_taper",
+    "hx_mask_discs", "hx_mask_distance", "hx_mask_taper", "hx_mask_polygons",
     "hx_deproject_gram", "hx_deproject_apply", "hx_alm_apply_cl",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
     "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
@@ -185,6 +185,7 @@ def load():
         L.hx_mask_discs.argtypes = [i, dp, C.c_int64, dp, dp, dp, C.c_double]
         L.hx_mask_distance.argtypes = [i, dp, C.c_double, dp]
         L.hx_mask_taper.argtypes = [i, dp, C.c_double, i, dp]
+        L.hx_mask_polygons.argtypes = [i, dp, C.c_int64, vp, dp, dp, C.c_double]
         L.hx_deproject_gram.argtypes = [C.c_int64, i, i, vp, i, vp, dp, dp]
         L.hx_deproject_apply.argtypes = [C.c_int64, i, i, vp, dp, i, vp, dp, vp]
         L.hx_alm_apply_cl.argtypes = [i, i, i, dp, dp, dp]

@@ -1,5 +1,5 @@
-// hx_masktools.hip -- disc holes, the distance to the nearest masked pixel and the C1 / C2 apodisation of a HEALPix mask (DESIGN.md
-// 4.20).  The definition lives in hx_masktools.h; this file is launch shape only.  gfx950 only.
+// hx_masktools.hip -- disc and convex-polygon holes, the distance to the nearest masked pixel and the C1 / C2 apodisation of a HEALPix
+// mask.  The definition lives in hx_masktools.h; this file is launch shape only.  gfx950 only.
 //
 //   k_mt_validate     one work item per pixel (work-groups stride over the map): the first pixel whose value is NaN or infinite
 //                     (atomicMin), the number of masked pixels (integer atomicAdd per work-group).
@@ -11,6 +11,11 @@
 //                     ring), 256 pixels per step with the running value carried; the ring's first and last masked index.
 //   k_mt_distance     one work item per pixel: hxmask::nearest_h over the tables; writes H, or mask x taper(H) (the fused epilogue).
 //                     Each work item reads mask[p] before it writes out[p] and the search reads the tables only: out may alias mask.
+//   k_mp_offsets      (polygons) one work item per polygon: the first vertex count outside 3 .. 64 (atomicMin).
+//   k_mp_check        one work item per polygon: its vertices and its signed edge normals (with rho and phi_e of each for the windows)
+//                     into two buffers, the first invalid polygon (atomicMin), the wide list by the pixel estimate of the bounding cap.
+//   k_mp_small        one work item per remaining polygon: the rings of its cap, the clipped window, the rule.
+//   k_mp_wide         one work-group per listed polygon: its edges staged in LDS once, waves over the rings, lanes over the window.
 // No floating-point atomics; vector stores only.
 #include <cstdlib>
 
@@ -100,6 +105,91 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_disc_wide(long long nside, long
     long long lo, hi;
     hxmask::disc_rings(nside, d, &lo, &hi);
     for (long long ir = lo + (threadIdx.x >> 6); ir <= hi; ir += MT_NW) disc_ring(nside, npix, ir, d, (int)(threadIdx.x & 63), 64, mask);
+}
+
+// ---- convex polygons ----
+// the first polygon whose vertex count lies outside POLY_MIN .. POLY_MAX (offsets[0] != 0 counts against polygon 0): no other kernel
+// reads offsets, lon or lat before this one has passed
+__global__ __launch_bounds__(MT_BLOCK) void k_mp_offsets(long long npoly, const long long *__restrict__ offsets, MtWords *__restrict__ words)
+{
+    const long long k = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (k >= npoly) return;
+    const long long a = offsets[k], n = offsets[k + 1] - a;
+    if ((k == 0 && a != 0) || !hxmask::count_valid(n)) atomicMin(&words->bad, (unsigned long long)k);
+}
+
+// one work item per polygon: its vertices into verts, validity (the first invalid polygon as 2 k + reason by atomicMin; reason 0: a
+// coordinate, 1: the shape), its edges into edges, and the wide list as for discs, by the estimated pixel count of the bounding cap
+__global__ __launch_bounds__(MT_BLOCK) void k_mp_check(long long nside, long long npoly, const long long *__restrict__ offsets, const double *__restrict__ lon,
+                                                      const double *__restrict__ lat, int force_wide, double *verts, hxmask::Edge *__restrict__ edges,
+                                                      MtWords *__restrict__ words, unsigned *__restrict__ wide)
+{
+    const long long k = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (k >= npoly) return;
+    const long long o = offsets[k];
+    const int n = (int)(offsets[k + 1] - o);
+    double *v = verts + 3 * o;
+    for (int i = 0; i < n; ++i) {
+        const double lo = lon[o + i], la = lat[o + i];
+        if (!hxmask::vertex_valid(lo, la)) {
+            atomicMin(&words->bad, 2ull * (unsigned long long)k);
+            return;
+        }
+        hxmask::make_vertex(lo, la, v + 3 * i);
+    }
+    int sigma;
+    if (!hxmask::poly_valid(n, v, &sigma)) {
+        atomicMin(&words->bad, 2ull * (unsigned long long)k + 1ull);
+        return;
+    }
+    for (int i = 0; i < n; ++i) edges[o + i] = hxmask::make_edge(v + 3 * i, v + 3 * (i + 1 < n ? i + 1 : 0), sigma);
+    hxmask::Disc cap;
+    const bool capped = hxmask::poly_cap(n, v, &cap);
+    if (force_wide || !capped || hxmask::disc_pixels(nside, cap.hr) > hxmask::WIDE_MIN) {
+        const unsigned long long i = atomicAdd(&words->count, 1ull);
+        if (i < (unsigned long long)npoly) wide[i] = (unsigned)k;
+    }
+}
+
+// the pixels k0 + lane0, k0 + lane0 + stride, ... of the window of the polygon on ring ir
+__device__ __forceinline__ void poly_ring(long long nside, long long npix, long long ir, bool capped, const hxmask::Disc &cap, int n, const hxmask::Edge *e,
+                                          int lane0, int stride, double value, double *mask)
+{
+    const hxmask::Ring r = hxmask::ring_info(nside, ir);
+    const hxmask::Window w = hxmask::poly_window(r, capped, cap, n, e);
+    for (long long i = lane0; i < w.count; i += stride) {
+        const long long j = hxmask::wrap_index(w.k0 + i, r.n), p = r.first + j;
+        if (p >= 0 && p < npix && hxmask::poly_hit(r, j, n, e)) mask[p] = value;
+    }
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void k_mp_small(long long nside, long long npix, long long npoly, const long long *__restrict__ offsets,
+                                                      const double *__restrict__ verts, const hxmask::Edge *__restrict__ edges, double value, double *mask)
+{
+    const long long k = (long long)blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (k >= npoly) return;
+    const long long o = offsets[k];
+    const int n = (int)(offsets[k + 1] - o);
+    hxmask::Disc cap;
+    if (!hxmask::poly_cap(n, verts + 3 * o, &cap) || hxmask::disc_pixels(nside, cap.hr) > hxmask::WIDE_MIN) return;
+    long long lo, hi;
+    hxmask::poly_rings(nside, true, cap, &lo, &hi);
+    for (long long ir = lo; ir <= hi; ++ir) poly_ring(nside, npix, ir, true, cap, n, edges + o, 0, 1, value, mask);
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void k_mp_wide(long long nside, long long npix, const unsigned *__restrict__ wide, const long long *__restrict__ offsets,
+                                                     const double *__restrict__ verts, const hxmask::Edge *__restrict__ edges, double value, double *mask)
+{
+    __shared__ hxmask::Edge lds[hxmask::POLY_MAX];
+    const long long k = (long long)wide[blockIdx.x], o = offsets[k];
+    const int n = (int)(offsets[k + 1] - o);
+    if ((int)threadIdx.x < n) lds[threadIdx.x] = edges[o + threadIdx.x];
+    hxmask::Disc cap;
+    const bool capped = hxmask::poly_cap(n, verts + 3 * o, &cap);
+    long long lo, hi;
+    hxmask::poly_rings(nside, capped, cap, &lo, &hi);
+    __syncthreads();
+    for (long long ir = lo + (threadIdx.x >> 6); ir <= hi; ir += MT_NW) poly_ring(nside, npix, ir, capped, cap, n, lds, (int)(threadIdx.x & 63), 64, value, mask);
 }
 
 // inclusive running maximum of v over the work-group in thread order; total: the maximum of all
@@ -290,6 +380,73 @@ extern "C" int hx_mask_discs(int nside, double *mask, int64_t ndisc, const doubl
             const unsigned long long part = nwide - done < 0x40000000ull ? nwide - done : 0x40000000ull;
             hipLaunchKernelGGL(k_mt_disc_wide, dim3((unsigned)part), dim3(MT_BLOCK), 0, st, (long long)nside, npix, wide.as<unsigned>() + done, vlon.as<double>(),
                                vlat.as<double>(), vrad.as<double>(), radius_all, vm.as<double>());
+        }
+    }
+    HX_HIP(hipGetLastError());
+    HX_TRY(vm.finish());
+    HX_HIP(hipStreamSynchronize(st));  // (the buffers are freed on return)
+    return HX_OK;
+}
+
+extern "C" int hx_mask_polygons(int nside, double *mask, int64_t npoly, const int64_t *offsets, const double *lon, const double *lat, double value)
+{
+    HX_TRY(ensure_ready());
+    if (nside < 1 || nside > 8192) return fail(HX_ERR_ARG, "hx_mask_polygons: nside = %d, 1 .. 8192 are supported", nside);
+    if (npoly < 0 || npoly > 0xffffffffll) return fail(HX_ERR_ARG, "hx_mask_polygons: npoly = %lld, 0 .. 2^32 - 1 are supported", (long long)npoly);
+    if (!mask || (npoly > 0 && (!offsets || !lon || !lat))) return fail(HX_ERR_ARG, "hx_mask_polygons: null pointer");
+    if (!hxmask::finite(value)) return fail(HX_ERR_ARG, "hx_mask_polygons: value is NaN or infinite");
+    const long long npix = 12ll * nside * nside;
+    const size_t bytes = sizeof(double) * (size_t)npix;
+    hipStream_t st = rt().stream;
+    OutView vm;  // in and out: a host map is uploaded here and copied back by finish()
+    HX_TRY(vm.bind(mask, bytes));
+    if (vm.host) HX_TRY(copy_h2d(vm.dev, mask, bytes));
+    DevBuf words, wide, verts, edges;
+    unsigned long long nmasked = 0;
+    HX_TRY(validate_mask("hx_mask_polygons", npix, vm.as<double>(), words, &nmasked));
+    if (npoly == 0) return HX_OK;
+    const char *hook = getenv("HX_MASK_WIDE");  // (tests) 1: every polygon down the wide path; read at every call
+    const bool force_wide = hook && hook[0] == '1';
+    // the offsets first: the number of vertices, and the bounds of every later read of lon and lat, come from them
+    InView voff, vlon, vlat;
+    HX_TRY(voff.bind(offsets, sizeof(long long) * (size_t)(npoly + 1)));
+    const MtWords init = {MT_CLEAR, 0ull};
+    MtWords got;
+    long long nvert = 0;
+    const unsigned nblocks = (unsigned)((npoly + MT_BLOCK - 1) / MT_BLOCK);
+    HX_HIP(hipMemcpyAsync(words.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mp_offsets, dim3(nblocks), dim3(MT_BLOCK), 0, st, (long long)npoly, voff.as<long long>(), words.as<MtWords>());
+    HX_HIP(hipGetLastError());
+    HX_HIP(hipMemcpyAsync(&got, words.p, sizeof(got), hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(&nvert, voff.as<long long>() + npoly, sizeof(nvert), hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    if (got.bad != MT_CLEAR)
+        return fail(HX_ERR_ARG, "hx_mask_polygons: polygon %llu has a vertex count outside 3 .. 64 (offsets must start at 0 and may not decrease)", got.bad);
+    HX_TRY(vlon.bind(lon, sizeof(double) * (size_t)nvert));
+    HX_TRY(vlat.bind(lat, sizeof(double) * (size_t)nvert));
+    HX_TRY(verts.alloc(sizeof(double) * 3 * (size_t)nvert));
+    HX_TRY(edges.alloc(sizeof(hxmask::Edge) * (size_t)nvert));
+    HX_TRY(wide.alloc(sizeof(unsigned) * (size_t)npoly));
+    HX_HIP(hipMemcpyAsync(words.p, &init, sizeof(init), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mp_check, dim3(nblocks), dim3(MT_BLOCK), 0, st, (long long)nside, (long long)npoly, voff.as<long long>(), vlon.as<double>(), vlat.as<double>(),
+                       force_wide ? 1 : 0, verts.as<double>(), edges.as<hxmask::Edge>(), words.as<MtWords>(), wide.as<unsigned>());
+    HX_HIP(hipGetLastError());
+    HX_HIP(hipMemcpyAsync(&got, words.p, sizeof(got), hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    if (got.bad != MT_CLEAR)
+        return fail(HX_ERR_ARG, (got.bad & 1ull) ? "hx_mask_polygons: polygon %llu is not convex (a repeated vertex, a collinear triple, a reflex vertex or antipodal neighbours)"
+                                                 : "hx_mask_polygons: polygon %llu has a NaN or infinite coordinate or |lat| > 90",
+                    got.bad >> 1);
+    const unsigned long long nwide = got.count < (unsigned long long)npoly ? got.count : (unsigned long long)npoly;
+    {
+        ProfScope prof("mask_polygons");
+        if (!force_wide && nwide < (unsigned long long)npoly)
+            hipLaunchKernelGGL(k_mp_small, dim3(nblocks), dim3(MT_BLOCK), 0, st, (long long)nside, npix, (long long)npoly, voff.as<long long>(), verts.as<double>(),
+                               edges.as<hxmask::Edge>(), value, vm.as<double>());
+        for (unsigned long long done = 0; done < nwide; done += 0x40000000ull) {
+            const unsigned long long part = nwide - done < 0x40000000ull ? nwide - done : 0x40000000ull;
+            hipLaunchKernelGGL(k_mp_wide, dim3((unsigned)part), dim3(MT_BLOCK), 0, st, (long long)nside, npix, wide.as<unsigned>() + done, voff.as<long long>(),
+                               verts.as<double>(), edges.as<hxmask::Edge>(), value, vm.as<double>());
         }
     }
     HX_HIP(hipGetLastError());

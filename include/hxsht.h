@@ -656,6 +656,21 @@ int hx_mask_discs(int nside, double *mask, int64_t ndisc, const double *lon, con
 int hx_mask_distance(int nside, const double *mask, double max_distance, double *H);
 int hx_mask_taper(int nside, const double *mask, double aposize, int kind, double *out);
 
+/* hx_mask_polygons: mask[p] = value for every pixel whose centre lies inside at least one of npoly convex spherical
+ * polygons.  Polygon k has the vertices offsets[k] .. offsets[k + 1] - 1 of lon, lat (degrees), 3 .. 64 of them, in either winding; its
+ * edges are the minor great-circle arcs between consecutive vertices.  With v_k = (cos lat cos lon, cos lat sin lon, sin lat),
+ * n_e = v_k x v_(k+1) (each component the difference of two products), d(u, e) = (n_x u_x + n_y u_y) + n_z u_z and sigma = +1 if
+ * d(v_2, e_0) > 0, else -1, all in float64 without fused multiply-adds: pixel p is inside iff sigma d(v_p, e) >= 0 for every edge --
+ * query_polygon, inclusive = False.  A polygon is valid iff sigma d(v_k, e) > 0 for every edge and every vertex that is not one of its
+ * endpoints (convex; no repeated vertex, collinear triple, reflex vertex or antipodal neighbours).  Every writer stores the same
+ * value: the result does not depend on the order of the polygons and is bit-identical from run to run.  value = 0.0 cuts holes; a map
+ * of zeros with value = 1.0 builds the union of tiles.  npoly = 0 writes nothing.  HX_ERR_ARG, nothing written (hx_last_error names
+ * the first such polygon or pixel): a NaN or infinite coordinate, |lat| > 90, a vertex count outside 3 .. 64, offsets not starting at
+ * 0 or decreasing, an invalid polygon, a NaN or infinite value, a NaN or infinite mask value.  offsets: [npoly + 1], host or device,
+ * as mask, lon and lat.  HX_MASK_WIDE=1 (tests) sends every polygon down the work-group-per-polygon path.  Profile name
+ * "mask_polygons". */
+int hx_mask_polygons(int nside, double *mask, int64_t npoly, const int64_t *offsets, const double *lon, const double *lat, double value);
+
 /* ---- template deprojection of maps ----------------------------------------------------------------------------------
  * A field's map d (already weighted by its mask v), its templates t_1 .. t_k (unmasked), f_i = v t_i; sums over pixels also run over
  * the ncomp components (1 for spin 0, else 2).  Maps and templates are [ncomp][npix] arrays, float64; `templates`, `maps` and `out`
