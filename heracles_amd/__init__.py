@@ -44,6 +44,7 @@ from .masks import apodize_mask, mask_discs, mask_distance, mask_polygons, recta
 from .deprojection import DeprojectionInfo, deproject_maps, deproject_templates, deprojection_bias
 from .mapping import catalog_alms, map_catalogs, transform
 from .mocks import gaussian_maps, mock_catalogs, poisson_catalog, synalm, synalm_components
+from .lognormal import lognormal_gaussian_cls, lognormal_maps, lognormal_realised_cls, nearest_psd_cls
 from .regions import jackknife_regions
 from .rotation import coord_matrix, euler_from_matrix, matrix_from_euler, rotate_alm, rotate_alms
 from .sht import Plan, get_plan
@@ -83,4 +84,5 @@ __all__ = [
     "mask_product_cls", "covariance_requests", "gaussian_covariance_coupled", "table_key",
     "mask_discs", "mask_polygons", "rectangle_polygons", "mask_distance", "apodize_mask",
     "deproject_templates", "deproject_maps", "deprojection_bias", "DeprojectionInfo",
+    "lognormal_gaussian_cls", "lognormal_realised_cls", "nearest_psd_cls", "lognormal_maps",
 ]

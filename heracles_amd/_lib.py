@@ -38,6 +38,7 @@ SYMBOLS = (
     "hx_synalm", "hx_cl_cholesky", "hx_mockcat_counts", "hx_mockcat_points", "hx_jk_regions", "hx_rotate_alm", "hx_gauss_cov_accumulate",
     "hx_mask_discs", "hx_mask_distance", "hx_mask_taper", "hx_mask_polygons",
     "hx_deproject_gram", "hx_deproject_apply", "hx_alm_apply_cl",
+    "hx_lognormal_xi", "hx_lognormal_maps", "hx_cl_nearest_psd",
     "hx_catmap_create", "hx_catmap_page", "hx_catmap_moments", "hx_catmap_finish", "hx_catmap_destroy",
     "hx_catalm_create", "hx_catalm_page", "hx_catalm_moments", "hx_catalm_finish", "hx_catalm_destroy",
     "hx_catmap_create_sel", "hx_catmap_page_sel", "hx_catmap_moments_sel", "hx_catmap_finish_sel", "hx_catmap_destroy_sel",
@@ -189,6 +190,9 @@ def load():
         L.hx_deproject_gram.argtypes = [C.c_int64, i, i, vp, i, vp, dp, dp]
         L.hx_deproject_apply.argtypes = [C.c_int64, i, i, vp, dp, i, vp, dp, vp]
         L.hx_alm_apply_cl.argtypes = [i, i, i, dp, dp, dp]
+        L.hx_lognormal_xi.argtypes = [i, i, i, dp, dp, dp]
+        L.hx_lognormal_maps.argtypes = [i, C.c_int64, dp, dp, dp, dp]
+        L.hx_cl_nearest_psd.argtypes = [i, i, dp, C.c_double, dp, dp]
         L.hx_catmap_create.restype = vp
         L.hx_catmap_create.argtypes = [C.c_int64, i, i, vp, vp]
         L.hx_catmap_page.argtypes = [vp, C.c_int64, vp]
@@ -294,7 +298,8 @@ def release_caches():
     ``naturalspice_batch`` read the same tables and keep nothing of their own; with ``exact_spin`` up to ``HX_XI_TABLES`` pair tables of
     0.31 GB each at lmax 6144 lie beside them), the Cholesky factor ``synalm`` keeps (23 MB at 30 components and lmax 6144), the folded
     coupling tables of ``gaussian_covariance_coupled`` ((spectra + 1) x bins x (lmax + 1) doubles: 0.22 GB at 465 spectra, 31 bins,
-    lmax 2048), the partial tiles and the reduced matrix of ``deproject_templates`` (at most ~72 MB): hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
+    lmax 2048), the partial tiles and the reduced matrix of ``deproject_templates`` (at most ~72 MB), the result and change report ``nearest_psd_cls``
+    stages before it copies them out (the size of its input): hx_release_caches.  The pixel weights ``compute_pixel_weights`` keeps (12 nside^2 doubles
     per result) and the pixel windows ``compute_pixel_window`` keeps go with them."""
     from . import pixwin, weights
 

@@ -127,6 +127,7 @@ void mixmat_drop_cache();
 void alm2cl_drop_cache();  // hx_twopoint.hip: the buffers hx_alm2cl_pairs keeps between calls
 void corr_cache_drop();    // hx_transforms.hip: nodes, weights and Wigner tables hx_cl2corr / hx_corr2cl keep for the last lmax
 void synalm_drop_cache();  // hx_synalm.hip: the factor hx_synalm / hx_cl_cholesky keep between calls
+void lognormal_drop_cache();  // hx_lognormal.hip: the result, change report, parameters and flag word its calls keep between calls
 int rotate_exec_flops(unsigned long long *v, bool reset);  // hx_rotate.hip: FP64 vector flops hx_rotate_alm executed (for hx_executed_flops)
 void gausscov_drop_cache();  // hx_gausscov.hip: the folded tables Z and coefficients hx_gauss_cov_accumulate keeps between calls
 int gausscov_exec_flops(unsigned long long *v, bool reset);  // hx_gausscov.hip: FP64 vector flops of hx_gauss_cov_accumulate (for hx_executed_flops)

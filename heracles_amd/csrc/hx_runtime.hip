@@ -476,6 +476,7 @@ int hx_init(int device)
         mixmat_drop_cache();
         alm2cl_drop_cache();
         synalm_drop_cache();
+        lognormal_drop_cache();
         gausscov_drop_cache();
         deproject_drop_cache();
         stager_reset_events();
@@ -502,6 +503,7 @@ int hx_release_caches(void)
     alm2cl_drop_cache();
     corr_cache_drop();
     synalm_drop_cache();
+    lognormal_drop_cache();
     gausscov_drop_cache();
     deproject_drop_cache();
     return HX_OK;

@@ -569,6 +569,29 @@ int hx_cov_shrink_sums(int n, int N, const double *x, const double *target, int6
 int hx_synalm(int ncomp, int lmax, const double *cl, uint64_t seed, uint32_t realisation, double *alms);
 int hx_cl_cholesky(int ncomp, int lmax, const double *cl, double *chol);
 
+/* ---- Lognormal mocks: Gaussianised spectra, repair of indefinite spectra, the map pass ---------------------------------
+ * hx_lognormal_xi: element-wise over correlation-function columns xi [ncol][nnodes], one factor per column (factor: host array [ncol]):
+ *   direction 0: out = log1p(xi * factor[c])   (to the Gaussian field: factor = 1 / (shift_i shift_j))
+ *   direction 1: out = factor[c] * expm1(xi)   (to the lognormal field: factor = shift_i shift_j)
+ *   in plain IEEE arithmetic, every operation rounded on its own.  out may be xi itself; any other overlap is HX_ERR_ARG.  Direction 0
+ *   with an argument of log1p that is <= -1 or NaN: HX_ERR_ARG, hx_last_error names the smallest (column, node), nothing is written.
+ *   Profile name "lognormal_xi".
+ * hx_lognormal_maps: out[r][p] = shift[r] * expm1(g[r][p] - sigma2[r] / 2) for nrow rows (1 .. 65535) of npix >= 1 doubles; sigma2 and
+ *   shift are host arrays [nrow] (shift > 0, sigma2 >= 0, finite).  out may be g itself; any other overlap is HX_ERR_ARG and nothing is
+ *   written.  One streaming pass.  Profile name "lognormal_maps".
+ * hx_cl_nearest_psd: cl and out packed as for hx_synalm, 1 <= ncomp <= 64.  Per l, with D = diag(C_l) and the components of C_jj = 0
+ *   left out (their rows and columns come back zero): R = D^-1/2 C D^-1/2 = V L V^T by cyclic Jacobi (round-robin order, until the largest
+ *   |off-diagonal| is <= 2^-50), C' = D^1/2 V max(L, floor) V^T D^1/2.  A matrix with no eigenvalue below floor is copied through bit for
+ *   bit.  floor < 0 selects the default 64 ncomp^2 2^-52, with which C' passes hx_cl_cholesky without a zeroed column; 0 <= floor < 1
+ *   otherwise.  change (may be NULL): [lmax + 1], max_ij |C'_ij - C_ij| / sqrt(C_ii C_jj), 0 where copied, +Inf where a non-zero entry
+ *   beside a zero auto-spectrum was removed.  out may be cl itself.  A negative auto-spectrum, NaN or Inf anywhere: HX_ERR_ARG,
+ *   hx_last_error names the smallest such l and the component; sweeps that do not converge: HX_ERR_UNSUPPORTED; nothing is written in
+ *   either case.  The same bits in every run and for every split of the l range.  The result and the change report of the last call
+ *   stay in HBM until hx_release_caches.  Profile name "cl_nearest_psd". */
+int hx_lognormal_xi(int direction, int ncol, int nnodes, const double *factor, const double *xi, double *out);
+int hx_lognormal_maps(int nrow, int64_t npix, const double *sigma2, const double *shift, const double *g, double *out);
+int hx_cl_nearest_psd(int ncomp, int lmax, const double *cl, double floor, double *out, double *change);
+
 /* ---- Poisson-sampled mock catalogues from expected-count maps ------------------------------------------------------
  * Both calls work on a range [pix_begin, pix_end) of RING pixels of `nside` (1 .. 8192, any integer); every array covers that range
  * only, so a catalogue can be made in pieces.  A realisation is a function of (seed, realisation, nside, pixel, index) alone.
