@@ -140,7 +140,7 @@ int corr_tables_view(int lmax, const double **T, const double **w, int *kpad);  
 // Gauss-Legendre nodes and their weights w, for hx_xi_cols.hip (built on first use; see PairCache for how long the pointers hold)
 int xi_pair_table_view(int lmax, int A, int B, const double **T, const double **w, int *kpad);
 
-// The two halves of hx_pointsht_adjoint (hx_nufft.hip), for callers that keep grids resident (hx_catalm, hx_mapper.hip).
+// The two halves of hx_pointsht_adjoint (hx_nufft.hip), for callers that keep grids resident (hx_catalm, hx_catalm.hip).
 // Half one: pointsht_order picks the spreading path for n points (tiles from 300000 points, HX_NUFFT_TILES forces it) and sorts them
 // by tile when that path is taken -- once for every component spread from these points; pointsht_spread_one ADDS one component
 // (val[n] at loc[n] = (theta, phi)) to grid [n1][n1], without clearing it.  The order lives in the buffers of `ps` until its next call.

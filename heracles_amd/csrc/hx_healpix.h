@@ -6,7 +6,7 @@
 // Every floating-point function rounds operation by operation (no contraction into fused multiply-adds), so that the host and the
 // device differ only where their sqrt / sin / cos / atan2 do.
 //
-// Not here: ang2pix (hx_mapper.hip; its device transcendentals have no host twin) and the plan's ring table (hx_plan.hip; it spells
+// Not here: ang2pix (hx_ang2pix.h; its device transcendentals have no host twin) and the plan's ring table (hx_plan.hip; it spells
 // the belt z as (2 nside - i) fact1, whose bits every SHT result depends on).
 #pragma once
 #include <cmath>

@@ -26,7 +26,7 @@
 // Step 1 is additive in the points and steps 2-4 are linear, so the transform has two halves with one owner each here (declared in
 // hx_common.h): "spread n points of one component into a given grid" (pointsht_order + pointsht_spread_one: no memset) and "grids to
 // alm" (pointsht_grids_to_alm).  hx_pointsht_adjoint is memset + half one + half two on the one grid the object owns; hx_catalm
-// (hx_mapper.hip) keeps one grid per component resident over the pages of a catalogue and runs half two once at the end.
+// (hx_catalm.hip) keeps one grid per component resident over the pages of a catalogue and runs half two once at the end.
 // The spread adds with hardware float64 atomics (global, and LDS in the tile kernel), whose order is not fixed: results agree from run
 // to run to rounding, NOT bit for bit.
 // The forward direction, alm -> values at the points (hx_pointsht_synthesis, hx_pointgrid_*), is the same chain transposed; it is

@@ -1,5 +1,5 @@
 // hx_sort.h -- stable LSD radix sort of (key, 32-bit value) pairs on the GPU, 8-bit digits.  Round 5: written for the two "next" rows that
-// sort -- catalogue points by pixel (hx_mapper.hip, heracles/healpy.py:144-160) and by LDS tile (hx_nufft.hip) --, which called a library
+// sort -- catalogue points by pixel (hx_mapper.hip, hx_catmap.hip, hx_catmap_sel.hip; heracles/healpy.py:144-160) and by LDS tile (hx_nufft.hip) --, which called a library
 // primitive until round 4.
 //
 // Per pass:  k_sort_hist     per tile of 4096 keys a 256-bin histogram (LDS atomics), written bin-major: counts[digit][tile];
@@ -266,6 +266,38 @@ inline int radix_sort_pairs_narrow(const long long *k64, unsigned *v0, unsigned 
     *ks = kcur;
     *vs = vcur;
     HX_HIP(hipGetLastError());
+    return HX_OK;
+}
+
+// The set-up every caller with 64-bit keys shares (hx_map_values, hx_catmap_page, hx_catmap_page_sel): end_bit from the largest key
+// `top`, the narrow sort when 32 bits hold it (unless `wide` forces the 64-bit one), and which sorted keys are live: k32 or k64, the
+// other null.  keys / idx: the input, overwritten; k2 (8 bytes per pair: two 32-bit key buffers or one 64-bit) and v1 grow as needed.
+// (A template, K = long long, so that only the units that call it instantiate the 64-bit sort kernels.)
+struct SortedPairs {
+    const unsigned *k32 = nullptr;
+    const long long *k64 = nullptr;
+    const unsigned *idx = nullptr;
+};
+
+template <class K>
+int sort_pairs_by_key(K *keys, unsigned *idx, unsigned long long n, unsigned long long top, bool wide, DevBuf &k2, DevBuf &v1, DevBuf &tmp,
+                      hipStream_t st, SortedPairs *out)
+{
+    int end_bit = 1;
+    while (end_bit < 64 && (1ull << end_bit) <= top) ++end_bit;
+    HX_TRY(k2.alloc(sizeof(long long) * (size_t)n));
+    HX_TRY(v1.alloc(sizeof(unsigned) * (size_t)n));
+    unsigned *vs = nullptr;
+    if (end_bit <= 32 && !wide) {
+        unsigned *ks = nullptr;
+        HX_TRY(radix_sort_pairs_narrow(keys, idx, k2.as<unsigned>(), k2.as<unsigned>() + n, v1.as<unsigned>(), n, end_bit, tmp, st, &ks, &vs));
+        out->k32 = ks;
+    } else {
+        K *ks = nullptr;
+        HX_TRY(radix_sort_pairs<K>(keys, idx, k2.as<K>(), v1.as<unsigned>(), n, end_bit, tmp, st, &ks, &vs));
+        out->k64 = ks;
+    }
+    out->idx = vs;
     return HX_OK;
 }
 

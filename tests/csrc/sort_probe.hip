@@ -1,5 +1,5 @@
-// sort_probe.hip -- test probe (tests/test_gpu_sort.py): calls the radix sort of hx_sort.h exactly as hx_mapper.hip and hx_nufft.hip
-// do -- scratch pairs and `tmp` from DevBufs, the library's stream -- and copies the sorted pairs out.  No sort logic of its own; not part
+// sort_probe.hip -- test probe (tests/test_gpu_sort.py): calls the radix sort of hx_sort.h exactly as hx_mapper.hip, the catalogue contexts
+// and hx_nufft.hip do -- scratch pairs and `tmp` from DevBufs, the library's stream -- and copies the sorted pairs out.  No sort logic of its own; not part
 // of the C ABI (include/hxsht.h).  Links against the in-tree libhxsht.so for the runtime (hx::rt, hx::ensure_ready, hx::fail, DevBuf).
 #include "hx_common.h"
 #include "hx_sort.h"
